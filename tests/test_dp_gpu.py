@@ -54,7 +54,7 @@ def test_two_rank_optimize_parameters_matches_big_batch(tmp_path):
 @pytest.mark.gpu
 def test_bench_with_eight_ranks_on_one_gpu():
     """``bench.py --gpus 8`` end to end, the eight ranks sharing this box's one GPU over gloo (APAMD_BENCH_SHARE_GPU=1
-    APAMD_DIST_BACKEND=gloo: test plumbing, the JSON line says so): the launcher re-executes under torch.distributed.run, every
+    APAMD_DIST_BACKEND=gloo: test plumbing, the JSON line says so): the launcher starts torch.distributed.run as a child, every
     rank builds its replica, rank 0's weights are broadcast, the DP train step runs with its collectives, and rank 0 prints ONE
     JSON line whose world size is 8 and whose replicas did not drift.  No scaling number is read off this -- the point is that the
     first real 8-GPU run is not also the first 8-rank run.  ``--no-parity-gate``: eight PROCESSES on one device run their kernels
@@ -71,7 +71,7 @@ def test_bench_with_eight_ranks_on_one_gpu():
                HSA_ENABLE_IPC_MODE_LEGACY='0', APAMD_BENCH_NO_TRAFFIC='1')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--train-steps', '1',
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--full', '--train-steps', '1',
                         '--no-stream', '--no-exact-fp32', '--no-cpu-baseline', '--no-parity-gate'], env=env, cwd=root, capture_output=True, text=True, timeout=1500)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
     assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stdout[-2000:], p.stderr[-3000:])

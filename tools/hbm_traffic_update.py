@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """profiles/hbm_traffic.json from the FETCH_SIZE / WRITE_SIZE passes of tools/pmc_prof.sh:
-    python tools/hbm_traffic_update.py <tag>      reads gpurun_out/<tag>_pmc_fetch.json and <tag>_pmc_write.json
+    python tools/hbm_traffic_update.py <tag>      reads $PROF_OUT/<tag>_pmc_fetch.json and <tag>_pmc_write.json
+(PROF_OUT as tools/pmc_prof.sh writes it, default prof_out/ in the repository root)
 Keys are the kernel names bench.py's LaunchProfiler uses (ap_conv2d_kernel_name; '+IN' for the in-kernel InstanceNorm form).
 bytes = FETCH_SIZE KiB x 1024 x 2 (the gfx950 correction of MI355X_MICROARCH.md for wide coalesced reads) + WRITE_SIZE KiB x 1024."""
 import json
@@ -9,9 +10,10 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get('PROF_OUT') or os.path.join(ROOT, 'prof_out')
 tag = sys.argv[1]
-fd = json.load(open(os.path.join(ROOT, 'gpurun_out', tag + '_pmc_fetch.json')))
-wd = json.load(open(os.path.join(ROOT, 'gpurun_out', tag + '_pmc_write.json')))
+fd = json.load(open(os.path.join(OUT, tag + '_pmc_fetch.json')))
+wd = json.load(open(os.path.join(OUT, tag + '_pmc_write.json')))
 path = os.path.join(ROOT, 'profiles', 'hbm_traffic.json')
 tab = json.load(open(path))
 
