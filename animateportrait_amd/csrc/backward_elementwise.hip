@@ -1129,7 +1129,10 @@ int ap_instnorm_bwd(const float* g1, int32_t g1_pad, const float* g2, const floa
 
 int ap_instnorm_bwd_split_ok(int32_t C, int32_t H, int32_t W, int32_t g1_pad) {
     const char* off = getenv("APAMD_NO_INBWD_SPLIT");      // (read per call: tests and A/B runs flip it inside one process)
-    return !(off && atoi(off)) && C >= 8 && C % 8 == 0 && H >= 3 && W >= 8 && W % 8 == 0 && H * W <= 4096 && (g1_pad == 0 || g1_pad == 1) ? 1 : 0;
+    // H >= 4 for the fold: the kernel adds padded row 0 into row 1 and padded row H + 1 into row H - 2 in the lanes of those rows,
+    // one border row per lane -- with H = 3 both land in row 1 and the second would be dropped
+    return !(off && atoi(off)) && C >= 8 && C % 8 == 0 && H >= 3 + g1_pad && W >= 8 && W % 8 == 0 && H <= 4096 && W <= 4096 &&
+           H * W <= 4096 && (g1_pad == 0 || g1_pad == 1) ? 1 : 0;
 }
 
 int ap_instnorm_bwd_split(const float* g1, int32_t g1_pad, const float* g2, const float* y, const float* mean, const float* rstd,
@@ -1141,7 +1144,7 @@ int ap_instnorm_bwd_split(const float* g1, int32_t g1_pad, const float* g2, cons
     if (!xs && !gt && !dy) return fail(AP_ERR_INVALID, "instnorm_bwd_split: no output requested");
     if (act < 0 || act > 2) return fail(AP_ERR_INVALID, "instnorm_bwd_split: act %d", act);
     if (!ap_instnorm_bwd_split_ok(C, H, W, g1_pad))
-        return fail(AP_ERR_UNSUPPORTED, "instnorm_bwd_split: C=%d %dx%d fold %d (needs C %% 8 == 0, W %% 8 == 0, H >= 3, H*W <= 4096)", C, H, W, g1_pad);
+        return fail(AP_ERR_UNSUPPORTED, "instnorm_bwd_split: C=%d %dx%d fold %d (needs C %% 8 == 0, W %% 8 == 0, H >= 3 + fold, H*W <= 4096)", C, H, W, g1_pad);
     if (N < 1 || N > 65535) return fail(AP_ERR_UNSUPPORTED, "instnorm_bwd_split: N=%d", N);
     InBwdSplitParams p;
     memset(&p, 0, sizeof(p));

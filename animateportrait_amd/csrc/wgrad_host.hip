@@ -760,13 +760,16 @@ int ap_conv_final_dgrad_bf16(const float* g, const float* w, int32_t N, int32_t 
 
 // ---- data gradient of the PatchGAN's output layer (dgrad_k7.h: dgrad_head_kernel)
 int32_t ap_conv_head_dgrad_bf16_ok(int32_t N, int32_t C, int32_t H, int32_t W) {
-    return (N >= 1 && C >= 32 && (C & 31) == 0 && H >= 2 && W >= 2 && H * W <= 1156 && (long long)N * (C / 32) < 2147483647LL) ? 1 : 0;
+    // H W <= 1156: the 32 output planes assembled in LDS; (H + 3) (W + 8) <= 7 * 256: the zero-framed gradient rows that
+    // dgrad_head_kernel stages with NI = 7 loads per thread (a long thin map within the first bound needs more: 6 x 192, 4 x 289)
+    return (N >= 1 && C >= 32 && (C & 31) == 0 && H >= 2 && W >= 2 && H <= 1156 && W <= 1156 && H * W <= 1156 &&
+            (H + 3) * (W + 8) <= 7 * 256 && (long long)N * (C / 32) < 2147483647LL) ? 1 : 0;
 }
 
 int ap_conv_head_dgrad_bf16(const float* g, const float* w, int32_t N, int32_t C, int32_t H, int32_t W, float* gx, ap_stream_t stream_) {
     if (!g || !w || !gx) return fail(AP_ERR_INVALID, "conv_head_dgrad_bf16: null pointer");
     if (!ap_conv_head_dgrad_bf16_ok(N, C, H, W))
-        return fail(AP_ERR_UNSUPPORTED, "conv_head_dgrad_bf16: N=%d C=%d %dx%d not served (C a multiple of 32, H W <= 1156)", N, C, H, W);
+        return fail(AP_ERR_UNSUPPORTED, "conv_head_dgrad_bf16: N=%d C=%d %dx%d not served (C a multiple of 32, H W <= 1156, (H + 3) (W + 8) <= 1792)", N, C, H, W);
     DgradHeadParams p;
     p.g = g; p.w = w; p.gx = gx; p.N = N; p.C = C; p.H = H; p.W = W;
     const size_t lds = (size_t)32 * H * W * 4 + (size_t)(H + 3) * 2 * (W + 8) * 2;

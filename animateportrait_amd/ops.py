@@ -1079,9 +1079,12 @@ def wgrad_xs_ok(k, stride, pad, pad_mode, g_shape, srcs, precision=None):
     if not XS_DIRECT or g_shape[1] <= 4:
         return False
     # the answer depends on the layer geometry and on WHICH forward copies the sources carry, not on their contents: cached, so
-    # that the backward pass of a launch-bound train step does not rebuild a descriptor and re-plan per layer and step
-    key = (k, stride, pad, pad_mode, tuple(g_shape), precision,
-           tuple((tuple(f.data.shape), f.xs is not None, f.s2d is not None, f.is_split_only) for f in srcs))
+    # that the backward pass of a launch-bound train step does not rebuild a descriptor and re-plan per layer and step.
+    # The key holds everything else the descriptor and the C-side plan read: the package mode (precision None, the head-only
+    # copies), the module switches, and the environment switches the library reads per call (tests and A/B runs flip them)
+    key = (k, stride, pad, pad_mode, tuple(g_shape), DEFAULT_PRECISION if precision is None else precision, DEFAULT_PRECISION,
+           XS_WGRAD, XS_DIRECT, tuple(os.environ.get(v) for v in _WGRAD_XS_ENV),
+           tuple((tuple(f.data.shape), f.xs is not None, f.s2d is not None, f.is_split_only, f.xs_heads_only) for f in srcs))
     hit = _WGRAD_XS_OK.get(key)
     if hit is None:
         d = _wgrad_desc(k, stride, pad, pad_mode, g_shape, None, srcs, precision)
@@ -1090,6 +1093,7 @@ def wgrad_xs_ok(k, stride, pad, pad_mode, g_shape, srcs, precision=None):
 
 
 _WGRAD_XS_OK = {}
+_WGRAD_XS_ENV = ('APAMD_NO_XS_DIRECT', 'APAMD_NO_XS_WGRAD', 'APAMD_NO_BF16X3', 'APAMD_NO_S2D_WGRAD', 'APAMD_ROWS_WGRAD')
 
 
 def wgrad_gt_dims(k, stride, pad, pad_mode, g_shape, srcs, precision=None):

@@ -376,7 +376,8 @@ int ap_conv_final_wgrad(const ap_src* src, const float* g, int32_t N, int32_t H,
  *   final_form = 1 (the last layer, networks.py:1277-1279; replaces ap_conv_final_wgrad in this arithmetic): wide = the layer's
  *       input (InstanceNorm + activation of wide->mean / rstd / act applied on the fly), narrow = the one-channel output gradient:
  *       dw[0][c][ky][kx] = sum g[n,0,y,x] * reflpad3(act(IN(src)))[n,c,y+ky,x+kx].
- * Served shapes: ap_wgrad_k7_bf16_ok() == 1 (W a multiple of 16 in 16..256, H >= 4); everything else AP_ERR_UNSUPPORTED.
+ * Served shapes: ap_wgrad_k7_bf16_ok() == 1 (wide C 32 | 64; narrow C 1 | 3 in the stem form, 1 in the final form; W a multiple of
+ * 16 in 16..256, H >= 4); everything else AP_ERR_UNSUPPORTED.
  * workspace: ap_wgrad_k7_bf16_workspace_floats() floats.  Fixed summation order. */
 int32_t ap_wgrad_k7_bf16_ok(int32_t N, int32_t wide_C, int32_t narrow_C, int32_t H, int32_t W, int32_t final_form);
 int64_t ap_wgrad_k7_bf16_workspace_floats(int32_t N, int32_t wide_C, int32_t narrow_C, int32_t H, int32_t W, int32_t final_form);
@@ -386,7 +387,7 @@ int ap_wgrad_k7_bf16(const ap_src* wide, const ap_src* narrow, int32_t N, int32_
  * matrix pipe (csrc/dgrad_k7.h): the gradient w.r.t. the PADDED input,
  *   gp[n][c][py][px] = sum_{ky,kx} w[0][c][ky][kx] * g[n][0][py-ky][px-kx],  py < H+6, px < W+6 (g zero outside),
  * to be folded over the reflection by its consumer (ap_instnorm_bwd / ap_fold_add with g1_pad = 3).  w: the layer's weight
- * [1][C][7][7].  Served: ap_conv_final_dgrad_bf16_ok() == 1 (W a multiple of 16 in 16..256). */
+ * [1][C][7][7].  Served: ap_conv_final_dgrad_bf16_ok() == 1 (C 32 | 64, any H >= 1, W a multiple of 16 in 16..256). */
 int32_t ap_conv_final_dgrad_bf16_ok(int32_t N, int32_t C, int32_t H, int32_t W);
 int64_t ap_conv_final_dgrad_bf16_workspace_floats(int32_t N, int32_t C, int32_t H, int32_t W);
 int ap_conv_final_dgrad_bf16(const float* g, const float* w, int32_t N, int32_t C, int32_t H, int32_t W, float* workspace, float* gp,
@@ -394,19 +395,21 @@ int ap_conv_final_dgrad_bf16(const float* g, const float* w, int32_t N, int32_t 
 /* Data gradient of the PatchGAN's output layer Conv2d(C, 1, 4, stride 1, pad 1) (networks.py:2643) in plain-bf16 arithmetic on the
  * bf16 matrix pipe (csrc/dgrad_k7.h):  gx[n][c][iy][ix] = sum_{ky,kx} w[0][c][ky][kx] * g[n][0][iy-ky+1][ix-kx+1]  (g: [N][1][H-1][W-1],
  * zero outside; w: the layer's weight [1][C][4][4]; gx: [N][C][H][W]).  Served: ap_conv_head_dgrad_bf16_ok() == 1 (C a multiple of 32,
- * H W <= 1156). */
+ * H, W >= 2, H W <= 1156 -- the 32 output planes of a workgroup in LDS -- and (H + 3) (W + 8) <= 1792 -- the zero-framed gradient
+ * rows, 7 loads per thread: 34 x 34 is served, a long thin map such as 6 x 192 is not). */
 int32_t ap_conv_head_dgrad_bf16_ok(int32_t N, int32_t C, int32_t H, int32_t W);
 int ap_conv_head_dgrad_bf16(const float* g, const float* w, int32_t N, int32_t C, int32_t H, int32_t W, float* gx, ap_stream_t stream);
 /* The PatchGAN's first layer, y = act(Conv2d(Cin = 1 | 2, 64, 4, stride 2, pad 1)(x) + bias) (networks.py:2620-2623), in plain-bf16
  * arithmetic on the bf16 matrix pipe as an output stream (csrc/conv_d0.h).  x: plain [N][Cin][H][W], w: the layer's weight
  * [64][Cin][4][4], bias [64] or NULL, act AP_ACT_NONE / RELU / LRELU, y [N][64][H/2][W/2].
- * Served: ap_conv_d0_fwd_bf16_ok() == 1 (even H, W a multiple of 4 up to 256). */
+ * Served: ap_conv_d0_fwd_bf16_ok() == 1 (Cout 64, even H >= 2, W a multiple of 4 in 8..256). */
 int32_t ap_conv_d0_fwd_bf16_ok(int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W);
 int ap_conv_d0_fwd_bf16(const float* x, const float* w, const float* bias, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W,
                         int32_t act, float* y, ap_stream_t stream);
 /* ... and its weight gradient, dw[m][c][ky][kx] = sum g[n,m,oy,ox] * zeropad1(x)[n,c,2oy+ky,2ox+kx] (g: [N][64][H/2][W/2] plain, x: the
  * layer's input), on the same kernel as ap_wgrad_k7_bf16 (form 2 of csrc/wgrad_k7.h: the gradient is read once).  Served:
- * ap_wgrad_d0_bf16_ok() == 1 (M = 64, Cin 1 | 2, even H, W a multiple of 32 up to 512 for one input channel, up to 448 for two). */
+ * ap_wgrad_d0_bf16_ok() == 1 (M = 64, Cin 1 | 2, even H >= 2, W a multiple of 32 up to 512 for one input channel, up to 480 for two:
+ * the two new input rows of a tile, Cin * 4 * (W / 2 + 16) / 8 16-byte loads each, fit two loads per thread). */
 int32_t ap_wgrad_d0_bf16_ok(int32_t N, int32_t M, int32_t Cin, int32_t H, int32_t W);
 int64_t ap_wgrad_d0_bf16_workspace_floats(int32_t N, int32_t M, int32_t Cin, int32_t H, int32_t W);
 int ap_wgrad_d0_bf16(const float* g, const float* x, int32_t N, int32_t M, int32_t Cin, int32_t H, int32_t W, float* workspace, float* dw,
@@ -437,7 +440,8 @@ int ap_instnorm_bwd(const float* g1, int32_t g1_pad, const float* g2, const floa
  *   strip fp32 [N][C][2][H]: dy[:, :, :, W-2:] transposed (the small second operand of a reflection-padded layer's data gradient), or NULL;
  *   dy    the fp32 gradient itself, or NULL.
  * heads_only: the consumers multiply head parts only (AP_PRECISION_BF16): tail planes are not written.
- * ap_instnorm_bwd_split_ok: 1 when the shape is served (C % 8 == 0, W % 8 == 0, H >= 3, H * W <= 4096, fold 0 or 1). */
+ * ap_instnorm_bwd_split_ok: 1 when the shape is served (C % 8 == 0, W % 8 == 0, H * W <= 4096, fold 0 with H >= 3 or fold 1 with
+ * H >= 4). */
 int ap_instnorm_bwd_split_ok(int32_t C, int32_t H, int32_t W, int32_t g1_pad);
 int ap_instnorm_bwd_split(const float* g1, int32_t g1_pad, const float* g2, const float* y, const float* mean, const float* rstd,
                           int32_t act, int32_t N, int32_t C, int32_t H, int32_t W, void* xs, void* gt, const int32_t* gt_dims,
