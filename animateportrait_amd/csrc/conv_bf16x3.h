@@ -652,7 +652,10 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
             const int oy0 = cur.ty * C::TH, ox0 = cur.tx * 32;
             const int co_base = cot * CO_TILE + wco * MT * 32;
             const bool want_stats = p.stats != nullptr;
-            const bool vec_ok = (p.o_rstride & 3) == 0 && p.osx == 1 && ox_off == 0;
+            // 16-byte fp32 stores of 4 pixels (the general loop's `full` form and fast32): every stride a multiple of 4 elements
+            // and y 16-byte aligned -- an output window (ap_out_view) may have any strides
+            const bool vec_ok = ((p.o_rstride | (int)p.o_cstride | (int)p.o_nstride) & 3) == 0 && p.osx == 1 && ox_off == 0 &&
+                                (reinterpret_cast<uintptr_t>(p.y) & 15) == 0;
             const bool full = vec_ok && ox0 + 32 <= p.OW;                      // whole 32-pixel rows: no per-element edge tests
             const int prow = lane >> 3, pcol = (lane & 7) * 4;
             const int oxv = ox0 + pcol;
@@ -937,8 +940,9 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
                                     for (int j = 0; j < 4; ++j)
                                         if (full || oxv + j < p.OW) { s4[ps] += vv[j]; q4[ps] += vv[j] * vv[j]; }
                                     // (an 8-byte store of four bf16 needs even element strides only: the 66-element rows of a padded
-                                    // data gradient qualify, which the 16-byte fp32 form does not)
-                                    const bool v16 = p.osx == 1 && ((p.o_rstride | (int)p.o_cstride | (int)p.o_nstride | ox_off) & 1) == 0;
+                                    // data gradient qualify, which the 16-byte fp32 form does not) and a 4-byte aligned y
+                                    const bool v16 = p.osx == 1 && ((p.o_rstride | (int)p.o_cstride | (int)p.o_nstride | ox_off) & 1) == 0 &&
+                                                     (reinterpret_cast<uintptr_t>(p.y) & 3) == 0;
                                     if (v16 && oxv + 3 < p.OW) {
                                         u32x2 pk;
                                         pk[0] = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)actf(vv[0])) |

@@ -172,7 +172,9 @@ int32_t ap_conv2d_pack_entries(const ap_conv_desc* d, const ap_weight_view* v, f
 int ap_conv2d_pack_run(const void* entries_dev, int32_t count, ap_stream_t stream);
 /* y = act(conv(src...) + bias); bias may be NULL; stat_partials may be NULL.
  * When stat_partials != NULL the epilogue also writes per-tile sum / sum of squares of the
- * pre-activation output for every (n, cout) (InstanceNorm2d statistics, networks.py:33-34). */
+ * pre-activation output for every (n, cout) (InstanceNorm2d statistics, networks.py:33-34).
+ * On the split-bf16 path y needs only element alignment: those kernels store 16 bytes at a time where Hout*Wout and Wout are
+ * multiples of 4 and y is 16-byte aligned (the rule of ap_out_view below, with the dense strides), narrower stores elsewhere. */
 int ap_conv2d_fwd(const ap_conv_desc* d, const float* packed, const float* bias, float* y,
                   float* stat_partials, ap_stream_t stream);
 /* ap_conv2d_fwd into a window: only output pixels oy < OH, ox < OW are computed, and y[n][co][oy][ox] is stored at
@@ -181,7 +183,12 @@ int ap_conv2d_fwd(const ap_conv_desc* d, const float* packed, const float* bias,
  * Used for the data gradient of the reflection-padded 3x3 layers (networks.py:2329-2421), whose padded-coordinate
  * output is 66 = 2 x 32 + 2 columns wide: the main launch computes columns 0..63 (two tile columns instead of
  * three), a second launch on the transposed last gradient columns writes the 2-column rest (rstride = 1,
- * xstride = row length). */
+ * xstride = row length).
+ * Any strides and any element-aligned y are accepted; the store width follows them.  16-byte stores (4 fp32 / 8 bf16
+ * pixels) need xstride = 1, x_off = 0, nstride, cstride and rstride multiples of 4 (fp32) / 8 (bf16) elements and a
+ * 16-byte aligned y; 8-byte stores of 4 bf16 pixels need xstride = 1, even x_off and strides and a 4-byte aligned y;
+ * everything else is stored element by element.  The window must lie inside the output: 1 <= OH <= Hout and
+ * 1 <= OW <= Wout (AP_ERR_INVALID otherwise); other plans than those named above are AP_ERR_UNSUPPORTED. */
 typedef struct ap_out_view {
     int64_t nstride, cstride;
     int32_t rstride, xstride, y_off, x_off, OH, OW;
