@@ -302,6 +302,16 @@ def conv_forward(tape, layer, srcs, norm_act=None, act=ACT_NONE, out_octet=False
     return out
 
 
+def _reduced(tape, f):
+    """The gradient of ``f`` as ONE plain tensor: its contributions taken off the tape, summed, the padded ones folded.  None
+    when nothing contributed."""
+    contribs = tape.take(f)
+    if not contribs:
+        return None
+    g1, pad, g2 = ops._split_contribs(contribs)
+    return g1 if (pad == 0 and g2 is None) else ops.fold_add(g1, pad, g2)
+
+
 def materialize_forward(tape, f, residual=None, consumer=None):
     """consumer: a ConvLayer that reads the result and is not a c -> c trunk layer; the fp32 tensor is dropped (inference)
     only if that layer, too, stages split copies (at ngf = 16 the first up-convolution, 64 -> 32, reads fp32)."""
@@ -311,11 +321,9 @@ def materialize_forward(tape, f, residual=None, consumer=None):
         tape.track(out)
 
         def bwd():
-            contribs = tape.take(out)
-            if not contribs:
+            g = _reduced(tape, out)
+            if g is None:
                 return
-            g1, pad, g2 = ops._split_contribs(contribs)
-            g = g1 if (pad == 0 and g2 is None) else ops.fold_add(g1, pad, g2)
             tape.add(f, g, 0)
             if residual is not None:
                 tape.add(residual, g, 0)
@@ -334,11 +342,9 @@ def warp_forward(tape, f, motion, flow, ifmask, level, consumer=None):
         tape.track(out)
 
         def bwd():
-            contribs = tape.take(out)
-            if not contribs or not tape.tracked(f):
+            g = _reduced(tape, out)
+            if g is None or not tape.tracked(f):
                 return
-            g1, pad, g2 = ops._split_contribs(contribs)
-            g = g1 if (pad == 0 and g2 is None) else ops.fold_add(g1, pad, g2)
             tape.add(f, ops.warp_concat_bwd(g, motion, flow, ifmask, level), 0)
         tape.steps.append(bwd)
     return out
@@ -352,12 +358,7 @@ def batch_split_forward(tape, f, b):
         tape.track(l2)
 
         def bwd():
-            parts = []
-            for part in (l1, l2):
-                contribs = tape.take(part)
-                g1, pad, g2 = ops._split_contribs(contribs)
-                parts.append(g1 if (pad == 0 and g2 is None) else ops.fold_add(g1, pad, g2))
-            tape.add(f, torch.cat(parts, 0), 0)
+            tape.add(f, torch.cat([_reduced(tape, l1), _reduced(tape, l2)], 0), 0)
         tape.steps.append(bwd)
     return l1, l2
 
@@ -399,10 +400,7 @@ class _NetFn(torch.autograd.Function):
             tape.backward()
             gin = [None] * ctx.n_inputs
             if ctx.in_feat is not None and tape.tracked(ctx.in_feat):
-                contribs = tape.take(ctx.in_feat)
-                if contribs:
-                    g1, pad, g2 = ops._split_contribs(contribs)
-                    gin[0] = g1 if (pad == 0 and g2 is None) else ops.fold_add(g1, pad, g2)
+                gin[0] = _reduced(tape, ctx.in_feat)
             if direct:       # already summed into the optimiser's flat gradient buffer (p.grad is a view of it)
                 tape.flush_block()
                 gp = [None] * len(ctx.params)

@@ -22,6 +22,13 @@ inline int check_launch(const char* what) {
     if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
     return AP_OK;
 }
+// An ap_src as a kernel's source segment (SrcSeg: data / mean / rstd / C / act / chunk_begin), into a zeroed parameter struct.
+// with_norm = false: the source is a split copy, normalised and activated by the pass that wrote it
+template <class Seg>
+inline void fill_seg(Seg& seg, const ap_src& s, int chunk_begin, bool with_norm = true) {
+    seg.data = s.data; seg.C = s.C; seg.chunk_begin = chunk_begin;
+    if (with_norm) { seg.mean = s.mean; seg.rstd = s.rstd; seg.act = s.act; }
+}
 // InstanceNorm statistics: planes with mean^2 > ratio * var (as estimated from the conv epilogue's fp32 sums) are
 // recomputed from the data (instnorm.hip: instnorm_finalize_kernel, conv_bf16x3.h: norm_split_kernel)
 constexpr float kInstNormRefineRatio = 32.f;

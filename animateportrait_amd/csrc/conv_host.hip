@@ -115,13 +115,20 @@ static int env_int(const char* name, int dflt) {
 
 static int num_cus();
 
-static int make_plan(const ap_conv_desc* d, Plan& pl) {
+// ------------------------------------------------------------------ make_plan, in steps
+struct Geom {
+    bool rowk;      // 1 x 7 over the row channels of a 7x7 stem (ap_split_prepass_rows): split-bf16 path only
+    int K;          // taps along x
+    int S, KT;      // kernel family: stride and dense tap count (0 = run-time taps)
+};
+
+// step 1: descriptor checks, kernel family, output size (pl.Hout, pl.Wout) and channel count (pl.Cin)
+static int plan_geometry(const ap_conv_desc* d, Plan& pl, Geom& g) {
     if (!d) return fail(AP_ERR_INVALID, "null descriptor");
     if (d->nsrc < 1 || d->nsrc > kMaxSeg) return fail(AP_ERR_INVALID, "nsrc=%d out of range", d->nsrc);
     if (d->N < 1 || d->H < 1 || d->W < 1 || d->Cout < 1) return fail(AP_ERR_INVALID, "bad dims");
-    // 1 x 7 over the row channels of a 7x7 stem (ap_split_prepass_rows): split-bf16 path only
-    const bool rowk = d->KH == 1 && d->KW == 7;
-    if (rowk) {
+    g.rowk = d->KH == 1 && d->KW == 7;
+    if (g.rowk) {
         if (d->transposed || d->stride != 1 || d->pad != 3 || d->nsrc != 1 || d->src[0].C != 32 ||
             d->precision == AP_PRECISION_FP32 || d->w_layout != AP_W_OIHW || d->w_flip)
             return fail(AP_ERR_UNSUPPORTED, "1x7 kernels exist only as the row form of a 7x7 stem (one 32-channel "
@@ -130,160 +137,161 @@ static int make_plan(const ap_conv_desc* d, Plan& pl) {
     } else if (d->KH != d->KW || d->KH < 1 || d->KH > 7) {
         return fail(AP_ERR_UNSUPPORTED, "kernel %dx%d", d->KH, d->KW);
     }
-    const int K = d->KW;
-    int S, KT;   // kernel family: stride and dense tap count (0 = run-time taps)
-    if (rowk) {
-        S = 1;
-        KT = K;
-        pl.Hout = d->H;
-        pl.Wout = d->W;
+    const int K = g.K = d->KW;
+    if (g.rowk) {
+        g.S = 1; g.KT = K;
+        pl.Hout = d->H; pl.Wout = d->W;
     } else if (!d->transposed) {
         if (d->stride != 1 && d->stride != 2) return fail(AP_ERR_UNSUPPORTED, "stride %d", d->stride);
-        S = d->stride;
-        KT = K;
+        g.S = d->stride; g.KT = K;
         if (K == 2) {
             // the space-to-depth form of a 4x4 stride-2 layer (ap_split_prepass_s2d): 4 run-time taps, split-bf16 only
             if (d->stride != 1 || d->pad != 0 || d->precision == AP_PRECISION_FP32 || d->w_layout != AP_W_OIHW || d->w_flip)
                 return fail(AP_ERR_UNSUPPORTED, "2x2 kernels exist only as the space-to-depth form of a 4x4 stride-2 layer "
                                                 "(stride 1, pad 0, split-bf16 precision)");
-            KT = 0;
+            g.KT = 0;
         } else if (K == 1) {
             // 1x1 convolution (channel_mapping of the intrinsic-flow regressor, intrinsic_flow_models/networks.py:23-24):
             // one run-time tap at offset (0, 0)
             if (d->stride != 1 || d->pad != 0) return fail(AP_ERR_UNSUPPORTED, "1x1 kernels: stride 1, pad 0 only");
-            KT = 0;
+            g.KT = 0;
         } else if (K != 3 && K != 4 && K != 7) {
             return fail(AP_ERR_UNSUPPORTED, "kernel size %d (built: 1, 3, 4, 7)", K);
         }
-        pl.Hout = (d->H + 2 * d->pad - K) / S + 1;
-        pl.Wout = (d->W + 2 * d->pad - K) / S + 1;
+        pl.Hout = (d->H + 2 * d->pad - K) / g.S + 1;
+        pl.Wout = (d->W + 2 * d->pad - K) / g.S + 1;
         if (d->pad_mode == AP_PAD_REFLECT && (d->pad >= d->H || d->pad >= d->W))
             return fail(AP_ERR_INVALID, "reflection pad %d >= input size", d->pad);
     } else {
         if (d->stride != 2) return fail(AP_ERR_UNSUPPORTED, "transposed conv needs stride 2");
         if (d->pad_mode != AP_PAD_ZERO) return fail(AP_ERR_UNSUPPORTED, "transposed conv with reflection pad");
-        S = 1;
-        KT = 0;
+        g.S = 1; g.KT = 0;
         pl.Hout = (d->H - 1) * 2 - 2 * d->pad + K + d->output_padding;
         pl.Wout = (d->W - 1) * 2 - 2 * d->pad + K + d->output_padding;
     }
     if (pl.Hout < 1 || pl.Wout < 1) return fail(AP_ERR_INVALID, "empty output");
-
-    int minC = 1 << 30;
     pl.Cin = 0;
     for (int s = 0; s < d->nsrc; ++s) {
         if (d->src[s].C < 1) return fail(AP_ERR_INVALID, "segment %d has C=%d", s, d->src[s].C);
         pl.Cin += d->src[s].C;
-        if (d->src[s].C < minC) minC = d->src[s].C;
     }
-    // 1..4 output channels, 7x7 'same' convolution: vector-ALU direct kernel (conv_direct.h)
-    if (rowk) {
-        const bool two_per_cu = true;
-        for (const auto& k : bf3_registry())
-            if (k.ROW && k.K == K && (!pl.bk || (two_per_cu ? k.TH < pl.bk->TH : k.TH > pl.bk->TH))) pl.bk = &k;
-        if (!pl.bk) return fail(AP_ERR_UNSUPPORTED, "no 1x%d row kernel", K);
+    return AP_OK;
+}
+
+// chunk layout: segment s starts at chunk chunk_begin[s] and takes ceil(C / ci) chunks of ci channels
+static void layout_chunks(const ap_conv_desc* d, Plan& pl, int ci) {
+    pl.nchunks = 0;
+    for (int s = 0; s < d->nsrc; ++s) {
+        pl.chunk_begin[s] = pl.nchunks;
+        pl.nchunks += (d->src[s].C + ci - 1) / ci;
     }
-    // (the PatchGAN's 4x4 pad-1 head, 512 -> 1 on 30 x 30 outputs, was tried here too: 160 workgroups of 128 chunks
-    // each run 0.60 ms against 0.39 ms on the MFMA kernel with a 1-of-32 filled tile)
-    if (!rowk && !d->transposed && d->stride == 1 && K == 7 && d->pad == 3 && d->Cout <= 4) {
-        pl.direct_cop = d->Cout == 1 ? 1 : 4;
-        const int ci = 4;
-        pl.nchunks = 0;
-        for (int s = 0; s < d->nsrc; ++s) {
-            pl.chunk_begin[s] = pl.nchunks;
-            pl.nchunks += (d->src[s].C + ci - 1) / ci;
-        }
-        pl.cin_pad = pl.nchunks * ci;
-        pl.packed_floats = (long long)pl.cin_pad * K * K * pl.direct_cop;
-        pl.stat_tiles = ((pl.Hout + 15) / 16) * ((pl.Wout + 63) / 64);
-        return AP_OK;
-    }
-    // PatchGAN output layer (one output channel, 4x4 pad 1; conv_head.h).  The weight image must not depend on the map
-    // size (weights are packed once per layer): layers of this shape carry their OIHW weights behind the regular image,
-    // and maps narrow enough for the half-wave row kernel use those.
-    const bool head_w = !rowk && !d->transposed && d->stride == 1 && K == 4 && d->Cout == 1 && d->nsrc == 1 && pl.Cin >= 64 &&
+    pl.cin_pad = pl.nchunks * ci;
+}
+
+// 1..4 output channels, 7x7 'same' convolution: vector-ALU direct kernel (conv_direct.h), no launch list
+// (the PatchGAN's 4x4 pad-1 head, 512 -> 1 on 30 x 30 outputs, was tried here too: 160 workgroups of 128 chunks
+// each run 0.60 ms against 0.39 ms on the MFMA kernel with a 1-of-32 filled tile)
+static bool plan_direct(const ap_conv_desc* d, const Geom& g, Plan& pl) {
+    if (g.rowk || d->transposed || d->stride != 1 || g.K != 7 || d->pad != 3 || d->Cout > 4) return false;
+    pl.direct_cop = d->Cout == 1 ? 1 : 4;
+    layout_chunks(d, pl, 4);
+    pl.packed_floats = (long long)pl.cin_pad * g.K * g.K * pl.direct_cop;
+    pl.stat_tiles = ((pl.Hout + 15) / 16) * ((pl.Wout + 63) / 64);
+    return true;
+}
+
+// narrow 3x3 layers (landmark encoder): memory streams, one lane per output pixel (conv_small.h)
+static bool plan_small(const ap_conv_desc* d, const Geom& g, Plan& pl) {
+    if (g.rowk || d->transposed || g.K != 3 || d->nsrc != 1 || pl.Cin > 16 || (d->Cout != 8 && d->Cout != 16) ||
+        d->w_layout != AP_W_OIHW || d->w_flip || env_int("APAMD_NO_SMALL", 0))
+        return false;
+    pl.small = true;
+    pl.nchunks = 1;
+    pl.cin_pad = pl.Cin;
+    pl.packed_floats = (long long)d->Cout * pl.Cin * 9;       // the OIHW weights as they are
+    pl.stat_tiles = ((pl.Hout + 7) / 8) * ((pl.Wout + 31) / 32);
+    return true;
+}
+
+// The two layers that carry a plain copy of their weights behind the regular packed image (returns whether this one does).
+// PatchGAN output layer (one output channel, 4x4 pad 1; conv_head.h): the weight image must not depend on the map size (weights
+// are packed once per layer), so layers of this shape carry their OIHW weights, and maps narrow enough for the half-wave row
+// kernel use those.  ConvTranspose2d(C, 1..4, 4, 2, 1): the data gradient of the PatchGAN's first layer w.r.t. the frame
+// (conv_tsmall.h); same arrangement with the IOHW weights.
+static bool plan_head_tsmall(const ap_conv_desc* d, const Geom& g, Plan& pl) {
+    const bool head_w = !g.rowk && !d->transposed && d->stride == 1 && g.K == 4 && d->Cout == 1 && d->nsrc == 1 && pl.Cin >= 64 &&
                         d->w_layout == AP_W_OIHW && !d->w_flip && d->pad == 1;
     pl.head = head_w && d->W <= kHeadMaxW;
-    // ConvTranspose2d(C, 1..4, 4, 2, 1): the data gradient of the PatchGAN's first layer w.r.t. the frame (conv_tsmall.h);
-    // same arrangement -- the IOHW weights ride behind the regular image
-    pl.tsmall = !rowk && d->transposed && d->stride == 2 && K == 4 && d->pad == 1 && d->output_padding == 0 && d->Cout <= 4 &&
+    pl.tsmall = !g.rowk && d->transposed && d->stride == 2 && g.K == 4 && d->pad == 1 && d->output_padding == 0 && d->Cout <= 4 &&
                 d->nsrc == 1 && d->w_layout == AP_W_IOHW && !d->w_flip;
-    // narrow 3x3 layers (landmark encoder): memory streams, one lane per output pixel (conv_small.h)
-    if (!rowk && !d->transposed && K == 3 && d->nsrc == 1 && pl.Cin <= 16 && (d->Cout == 8 || d->Cout == 16) &&
-        d->w_layout == AP_W_OIHW && !d->w_flip && !env_int("APAMD_NO_SMALL", 0)) {
-        pl.small = true;
-        pl.nchunks = 1;
-        pl.cin_pad = pl.Cin;
-        pl.packed_floats = (long long)d->Cout * pl.Cin * 9;       // the OIHW weights as they are
-        pl.stat_tiles = ((pl.Hout + 7) / 8) * ((pl.Wout + 31) / 32);
+    return head_w || pl.tsmall;
+}
+
+// The split-bf16 matrix path (conv_bf16x3.h) and its kernel, pl.bk (left null: the layer stays on the fp32 kernel): the row form
+// of a stem, and wide 3x3 / 4x4 / transposed layers when the caller allows ~1e-4 relative error (>= 48 outputs fill most of a
+// 64-cout tile; with >= 128 inputs even a 16-output layer -- the data gradient of a ResnetBlock2 convolution w.r.t. its
+// 16-channel landmark segments -- is 3x faster here than on the fp32 pipe)
+static int pick_bf3(const ap_conv_desc* d, const Geom& g, Plan& pl) {
+    const int K = g.K, KT = g.KT;
+    if (g.rowk) {
+        // the shortest row tile: two workgroups per CU
+        for (const auto& k : bf3_registry())
+            if (k.ROW && k.K == K && (!pl.bk || k.TH < pl.bk->TH)) pl.bk = &k;
+        return pl.bk ? AP_OK : fail(AP_ERR_UNSUPPORTED, "no 1x%d row kernel", K);
+    }
+    if (d->precision == AP_PRECISION_FP32 || !(d->Cout >= 48 || (d->Cout >= 16 && pl.Cin >= 128)) || pl.Cin < 32 ||
+        env_int("APAMD_NO_BF16X3", 0))
         return AP_OK;
-    }
-    // split-bf16 matrix path (conv_bf16x3.h): wide 3x3 / transposed layers when the caller allows ~1e-4 relative error
-    // (>= 48 outputs fill most of a 64-cout tile; with >= 128 inputs even a 16-output layer -- the data gradient of a
-    // ResnetBlock2 convolution w.r.t. its 16-channel landmark segments -- is 3x faster here than on the fp32 pipe)
-    if (!rowk && d->precision != AP_PRECISION_FP32 && (d->Cout >= 48 || (d->Cout >= 16 && pl.Cin >= 128)) && pl.Cin >= 32 &&
-        !env_int("APAMD_NO_BF16X3", 0)) {
-        bool seg_ok = true;
-        for (int s = 0; s < d->nsrc; ++s) seg_ok = seg_ok && d->src[s].C % 16 == 0;
-        if (seg_ok && (KT == 0 || K == 3 || (K == 4 && S == 1))) {
-            // several tile heights of a family: the tallest one (best operand reuse) unless its tile list leaves
-            // most CUs idle (streaming inference at batch 1..4), then the shortest
-            const Bf3Kernel* tall = nullptr;
-            const Bf3Kernel* small = nullptr;
-            for (const auto& k : bf3_registry())
-                if (k.S == S && k.K == KT && !k.ROW) {
-                    if (!tall || k.TH >= tall->TH) tall = &k;
-                    if (!small || k.TH < small->TH) small = &k;
-                }
-            pl.bk = tall;
-            if (KT == 0) {
-                // every launch of these plans has 4 taps (2x2 layers, 4x4 phases, fused 3x3 phases of an even output)
-                const bool all4 = K == 2 || K == 4 || (d->transposed && K == 3 && pl.Hout % 2 == 0 && pl.Wout % 2 == 0);
-                pl.k0_small = all4;
-                if (pl.k0_small) pl.bk = small;
-                // stride-2 transposed 3x3 / 4x4 with pad 1 and an even output: all four phases in one tile
-                if (d->transposed && (K == 3 || K == 4) && d->pad == 1 && d->stride == 2 && pl.Hout % 2 == 0 && pl.Wout % 2 == 0 &&
-                    true) {
-                    pl.ph4 = K;
-                    pl.bk = ph4_kernel(K);
-                }
-            }
-            if (tall && small != tall && KT != 0) {
-                const long long tiles = (long long)d->N * ((pl.Hout + tall->TH - 1) / tall->TH) * ((pl.Wout + 31) / 32) *
-                                        ((d->Cout + tall->CO_TILE - 1) / tall->CO_TILE);
-                // (also for maps no taller than the short tile: the column strip of a reflection-padded data gradient)
-                if ((tiles * 2 <= num_cus() || pl.Hout <= small->TH) && !env_int("APAMD_NO_SMALL_TILES", 0)) pl.bk = small;
-            }
+    for (int s = 0; s < d->nsrc; ++s)
+        if (d->src[s].C % 16 != 0) return AP_OK;
+    if (!(KT == 0 ? K <= 4 : (K == 3 || (K == 4 && g.S == 1)))) return AP_OK;
+    // several tile heights of a family: the tallest one (best operand reuse) unless its tile list leaves
+    // most CUs idle (streaming inference at batch 1..4), then the shortest
+    const Bf3Kernel *tall = nullptr, *small = nullptr;
+    for (const auto& k : bf3_registry())
+        if (k.S == g.S && k.K == KT && !k.ROW) {
+            if (!tall || k.TH >= tall->TH) tall = &k;
+            if (!small || k.TH < small->TH) small = &k;
         }
-        if (KT == 0 && K != 1 && K != 2 && K != 3 && K != 4) pl.bk = nullptr;
-    }
-    if (pl.bk) {
-        pl.bf3 = true;
-        pl.nchunks = 0;
-        for (int s = 0; s < d->nsrc; ++s) {
-            pl.chunk_begin[s] = pl.nchunks;
-            pl.nchunks += d->src[s].C / 16;
+    pl.bk = tall;
+    const bool even_out = pl.Hout % 2 == 0 && pl.Wout % 2 == 0;
+    if (KT == 0) {
+        // every launch of these plans has 4 taps (2x2 layers, 4x4 phases, fused 3x3 phases of an even output): half-height tile
+        pl.k0_small = K == 2 || K == 4 || (d->transposed && K == 3 && even_out);
+        if (pl.k0_small) pl.bk = small;
+        // stride-2 transposed 3x3 / 4x4 with pad 1 and an even output: all four phases in one tile
+        if (d->transposed && (K == 3 || K == 4) && d->pad == 1 && d->stride == 2 && even_out) {
+            pl.ph4 = K;
+            pl.bk = ph4_kernel(K);
         }
-        pl.cin_pad = pl.nchunks * 16;              // channels that exist in the sources
-        pl.nchunks = (pl.nchunks + 1) & ~1;        // the kernel's pipeline runs chunk pairs: pad with an all-zero chunk
-        pl.co_tiles = (d->Cout + pl.bk->CO_TILE - 1) / pl.bk->CO_TILE;
-    } else {
-    // tile configuration by output width
+    } else if (tall && small != tall) {
+        const long long tiles = (long long)d->N * ((pl.Hout + tall->TH - 1) / tall->TH) * ((pl.Wout + 31) / 32) *
+                                ((d->Cout + tall->CO_TILE - 1) / tall->CO_TILE);
+        // (also for maps no taller than the short tile: the column strip of a reflection-padded data gradient)
+        if ((tiles * 2 <= num_cus() || pl.Hout <= small->TH) && !env_int("APAMD_NO_SMALL_TILES", 0)) pl.bk = small;
+    }
+    return AP_OK;
+}
+
+// The fp32 implicit-GEMM kernel (conv_igemm.h), pl.k: cout tile by output width, channel chunk by the segments and the LDS budget
+static int pick_igemm(const ap_conv_desc* d, const Geom& g, Plan& pl) {
     int co_tile = d->Cout >= 96 ? 128 : (d->Cout >= 48 ? 64 : 32);
     co_tile = env_int("APAMD_CONV_COTILE", co_tile);
     // channel chunk: largest of {8,4,2} that does not over-pad the narrowest segment, then shrink
     // until two workgroups fit a CU's LDS
+    int minC = 1 << 30;
+    for (int s = 0; s < d->nsrc; ++s) minC = std::min(minC, (int)d->src[s].C);
     int ci = minC <= 2 ? 2 : (minC <= 4 ? 4 : 8);
     for (int s = 0; s < d->nsrc; ++s)
         while (ci > 2 && d->src[s].C % ci != 0 && d->src[s].C > ci) ci >>= 1;
-    int ntaps_max = d->transposed ? ((K + 1) / 2) * ((K + 1) / 2) : K * K;
+    const int ntaps_max = d->transposed ? ((g.K + 1) / 2) * ((g.K + 1) / 2) : g.K * g.K;
     const size_t lds_target = (size_t)env_int("APAMD_CONV_LDS_TARGET", 72 * 1024);
     for (;;) {
-        const ConvKernelInfo* k = find_kernel(ci, S, KT, co_tile);
-        if (!k) return fail(AP_ERR_UNSUPPORTED, "no kernel for CI=%d S=%d K=%d CO_TILE=%d", ci, S, KT, co_tile);
+        const ConvKernelInfo* k = find_kernel(ci, g.S, g.KT, co_tile);
+        if (!k) return fail(AP_ERR_UNSUPPORTED, "no kernel for CI=%d S=%d K=%d CO_TILE=%d", ci, g.S, g.KT, co_tile);
         int nch = 0;
         for (int s = 0; s < d->nsrc; ++s) nch += (d->src[s].C + ci - 1) / ci;
-        size_t bytes = 4 * k->lds_floats(ntaps_max, nch > 1 ? 2 : 1, nch * ci);
+        const size_t bytes = 4 * k->lds_floats(ntaps_max, nch > 1 ? 2 : 1, nch * ci);
         if (bytes <= lds_target || ci == 2) {
             if (bytes > 160 * 1024) return fail(AP_ERR_UNSUPPORTED, "LDS tile of %zu bytes does not fit", bytes);
             pl.k = k;
@@ -291,97 +299,111 @@ static int make_plan(const ap_conv_desc* d, Plan& pl) {
         }
         ci >>= 1;
     }
-    {
-        int forced = env_int("APAMD_CONV_CI", 0);
-        if (forced) {
-            const ConvKernelInfo* k = find_kernel(forced, S, KT, co_tile);
-            if (k) { pl.k = k; ci = forced; }
-        }
+    if (const int forced = env_int("APAMD_CONV_CI", 0)) {
+        if (const ConvKernelInfo* k = find_kernel(forced, g.S, g.KT, co_tile)) { pl.k = k; ci = forced; }
     }
-    pl.nchunks = 0;
-    for (int s = 0; s < d->nsrc; ++s) {
-        pl.chunk_begin[s] = pl.nchunks;
-        pl.nchunks += (d->src[s].C + ci - 1) / ci;
-    }
-    pl.cin_pad = pl.nchunks * ci;
+    layout_chunks(d, pl, ci);
     pl.co_tiles = (d->Cout + co_tile - 1) / co_tile;
-    }
+    return AP_OK;
+}
 
-    auto finish = [&](Launch& L) {
-        L.tiles_x = (L.OW + 31) / 32;
-        const int th = pl.bk ? pl.bk->TH : pl.k->TH;
-        const int wf = pl.bk ? pl.bk->wfloats((int)L.taps.size()) : pl.k->wfloats((int)L.taps.size());
-        L.tiles_y = (L.OH + th - 1) / th;
-        L.wp_off = pl.packed_floats;
-        L.stat_tile_off = pl.stat_tiles;
-        pl.packed_floats += (long long)pl.co_tiles * pl.nchunks * wf;
-        pl.stat_tiles += L.tiles_x * L.tiles_y;
-    };
-    if (!d->transposed) {
-        Launch L;
-        for (int ky = 0; ky < (rowk ? 1 : K); ++ky)
-            for (int kx = 0; kx < K; ++kx) {
-                Tap t;
-                t.ly = ky;
-                t.lx = kx;
-                t.ky = d->w_flip ? K - 1 - ky : ky;
-                t.kx = d->w_flip ? K - 1 - kx : kx;
-                L.taps.push_back(t);
+// a finished launch takes its tile grid, its weight block and its statistics tiles
+static void add_launch(Plan& pl, Launch& L) {
+    const int ntaps = (int)L.taps.size();
+    const int th = pl.bk ? pl.bk->TH : pl.k->TH;
+    const int wf = pl.bk ? pl.bk->wfloats(ntaps) : pl.k->wfloats(ntaps);
+    L.tiles_x = (L.OW + 31) / 32;
+    L.tiles_y = (L.OH + th - 1) / th;
+    L.wp_off = pl.packed_floats;
+    L.stat_tile_off = pl.stat_tiles;
+    pl.packed_floats += (long long)pl.co_tiles * pl.nchunks * wf;
+    pl.stat_tiles += L.tiles_x * L.tiles_y;
+    pl.launches.push_back(L);
+}
+
+static void dense_launch(const ap_conv_desc* d, const Geom& g, Plan& pl) {
+    const int K = g.K;
+    Launch L;
+    for (int ky = 0; ky < (g.rowk ? 1 : K); ++ky)
+        for (int kx = 0; kx < K; ++kx) L.taps.push_back(Tap{d->w_flip ? K - 1 - ky : ky, d->w_flip ? K - 1 - kx : kx, ky, kx});
+    L.OH = pl.Hout; L.OW = pl.Wout;
+    L.dy0 = g.rowk ? 0 : -d->pad; L.dx0 = -d->pad;
+    L.osy = L.osx = 1; L.oy_off = L.ox_off = 0;
+    add_launch(pl, L);
+}
+
+// ConvTranspose2d stride 2 as sub-pixel phases:
+// y[co, 2q+ph] = sum over taps k with (ph + pad - k) even of x[ci, q + (ph + pad - k)/2] * w[ci,co,k]
+// Split-bf16 path, even output size: the four phases share one pixel-tile grid and run as ONE launch whose
+// cout tiles enumerate (phase, cout tile) -- the activation tile is fetched from HBM once instead of four
+// times and the interleaved output lines of the phases meet in the XCD's L2 (conv_bf16x3.h, ConvKParams.nphase).
+static int phase_launches(const ap_conv_desc* d, const Geom& g, Plan& pl) {
+    const int K = g.K;
+    const bool fuse = pl.bk != nullptr && pl.Hout % 2 == 0 && pl.Wout % 2 == 0;
+    for (int phy = 0; phy < 2; ++phy)
+        for (int phx = 0; phx < 2; ++phx) {
+            Launch L;
+            L.OH = (pl.Hout - phy + 1) / 2;
+            L.OW = (pl.Wout - phx + 1) / 2;
+            if (L.OH < 1 || L.OW < 1) continue;
+            std::vector<std::pair<int, int>> ys, xs;  // (k, shift)
+            for (int k = 0; k < K; ++k) {
+                if (((phy + d->pad - k) % 2 + 2) % 2 == 0) ys.push_back({k, (phy + d->pad - k) / 2});
+                if (((phx + d->pad - k) % 2 + 2) % 2 == 0) xs.push_back({k, (phx + d->pad - k) / 2});
             }
-        L.OH = pl.Hout; L.OW = pl.Wout;
-        L.dy0 = rowk ? 0 : -d->pad; L.dx0 = -d->pad;
-        L.osy = L.osx = 1; L.oy_off = L.ox_off = 0;
-        finish(L);
-        pl.launches.push_back(L);
+            int miny = 1 << 30, minx = 1 << 30, maxy = -(1 << 30), maxx = -(1 << 30);
+            for (auto& a : ys) { miny = std::min(miny, a.second); maxy = std::max(maxy, a.second); }
+            for (auto& a : xs) { minx = std::min(minx, a.second); maxx = std::max(maxx, a.second); }
+            if (ys.empty() || xs.empty() || maxy - miny > 1 || maxx - minx > 1)
+                return fail(AP_ERR_UNSUPPORTED, "transposed conv k=%d pad=%d not decomposable", K, d->pad);
+            for (auto& a : ys)
+                for (auto& b : xs)
+                    L.taps.push_back(Tap{d->w_flip ? K - 1 - a.first : a.first, d->w_flip ? K - 1 - b.first : b.first,
+                                         a.second - miny, b.second - minx});
+            L.dy0 = miny; L.dx0 = minx;
+            L.osy = L.osx = 2; L.oy_off = phy; L.ox_off = phx;
+            if (fuse) {
+                // one launch for the four phases: every phase carries the whole 2 x 2 window (positions it does
+                // not have get zero weights), in the fixed order t = ly * 2 + lx
+                std::vector<Tap> win(4, Tap{-1, -1, 0, 0});
+                for (int t = 0; t < 4; ++t) { win[t].ly = t >> 1; win[t].lx = t & 1; }
+                for (const auto& t : L.taps) { win[t.ly * 2 + t.lx].ky = t.ky; win[t.ly * 2 + t.lx].kx = t.kx; }
+                L.taps = win;
+            }
+            add_launch(pl, L);
+        }
+    pl.fused_phases = fuse && pl.launches.size() == 4;
+    return AP_OK;
+}
+
+static int make_plan(const ap_conv_desc* d, Plan& pl) {
+    Geom g;
+    int rc = plan_geometry(d, pl, g);
+    if (rc) return rc;
+    if (plan_direct(d, g, pl) || plan_small(d, g, pl)) return AP_OK;
+    const bool plain_w = plan_head_tsmall(d, g, pl);
+    rc = pick_bf3(d, g, pl);
+    if (rc) return rc;
+    if (pl.bk) {
+        // step 3, chunk layout: 16 channels of the split sources per chunk
+        pl.bf3 = true;
+        layout_chunks(d, pl, 16);                  // cin_pad: channels that exist in the sources
+        pl.nchunks = (pl.nchunks + 1) & ~1;        // the kernel's pipeline runs chunk pairs: pad with an all-zero chunk
+        pl.co_tiles = (d->Cout + pl.bk->CO_TILE - 1) / pl.bk->CO_TILE;
     } else {
-        // y[co, 2q+ph] = sum over taps k with (ph + pad - k) even of x[ci, q + (ph + pad - k)/2] * w[ci,co,k]
-        // Split-bf16 path, even output size: the four phases share one pixel-tile grid and run as ONE launch whose
-        // cout tiles enumerate (phase, cout tile) -- the activation tile is fetched from HBM once instead of four
-        // times and the interleaved output lines of the phases meet in the XCD's L2 (conv_bf16x3.h, ConvKParams.nphase).
-        const bool fuse = pl.bk != nullptr && pl.Hout % 2 == 0 && pl.Wout % 2 == 0;
-        for (int phy = 0; phy < 2; ++phy)
-            for (int phx = 0; phx < 2; ++phx) {
-                Launch L;
-                L.OH = (pl.Hout - phy + 1) / 2;
-                L.OW = (pl.Wout - phx + 1) / 2;
-                if (L.OH < 1 || L.OW < 1) continue;
-                std::vector<std::pair<int, int>> ys, xs;  // (k, shift)
-                for (int k = 0; k < K; ++k) {
-                    if (((phy + d->pad - k) % 2 + 2) % 2 == 0) ys.push_back({k, (phy + d->pad - k) / 2});
-                    if (((phx + d->pad - k) % 2 + 2) % 2 == 0) xs.push_back({k, (phx + d->pad - k) / 2});
-                }
-                int miny = 1 << 30, minx = 1 << 30, maxy = -(1 << 30), maxx = -(1 << 30);
-                for (auto& a : ys) { miny = std::min(miny, a.second); maxy = std::max(maxy, a.second); }
-                for (auto& a : xs) { minx = std::min(minx, a.second); maxx = std::max(maxx, a.second); }
-                if (ys.empty() || xs.empty() || maxy - miny > 1 || maxx - minx > 1)
-                    return fail(AP_ERR_UNSUPPORTED, "transposed conv k=%d pad=%d not decomposable", K, d->pad);
-                for (auto& a : ys)
-                    for (auto& b : xs) {
-                        Tap t;
-                        t.ky = d->w_flip ? K - 1 - a.first : a.first;
-                        t.kx = d->w_flip ? K - 1 - b.first : b.first;
-                        t.ly = a.second - miny;
-                        t.lx = b.second - minx;
-                        L.taps.push_back(t);
-                    }
-                L.dy0 = miny; L.dx0 = minx;
-                L.osy = L.osx = 2; L.oy_off = phy; L.ox_off = phx;
-                if (fuse) {
-                    // one launch for the four phases: every phase carries the whole 2 x 2 window (positions it does
-                    // not have get zero weights), in the fixed order t = ly * 2 + lx
-                    std::vector<Tap> win(4, Tap{-1, -1, 0, 0});
-                    for (int t = 0; t < 4; ++t) { win[t].ly = t >> 1; win[t].lx = t & 1; }
-                    for (const auto& t : L.taps) { win[t.ly * 2 + t.lx].ky = t.ky; win[t.ly * 2 + t.lx].kx = t.kx; }
-                    L.taps = win;
-                }
-                finish(L);
-                pl.launches.push_back(L);
-            }
-        pl.fused_phases = fuse && pl.launches.size() == 4;
+        rc = pick_igemm(d, g, pl);
+        if (rc) return rc;
     }
-    if (head_w || pl.tsmall) {
+    // step 4: the launch list
+    if (d->transposed) {
+        rc = phase_launches(d, g, pl);
+        if (rc) return rc;
+    } else {
+        dense_launch(d, g, pl);
+    }
+    if (plain_w) {
         pl.head_w_off = (pl.packed_floats + 3) & ~3LL;            // float4 loads
-        pl.packed_floats = pl.head_w_off + (long long)pl.Cin * d->Cout * K * K;
+        pl.packed_floats = pl.head_w_off + (long long)pl.Cin * d->Cout * g.K * g.K;
     }
     return AP_OK;
 }
@@ -686,28 +708,12 @@ int ap_conv2d_kernel_name(const ap_conv_desc* d, char* buf, int32_t buflen) {
     int rc = make_plan(d, pl);
     if (rc) return rc;
     if (!buf || buflen < 1) return fail(AP_ERR_INVALID, "kernel_name: bad buffer");
-    if (pl.direct_cop) {
-        snprintf(buf, buflen, "DirectCfg<%d, %d>", d->KH, pl.direct_cop);
-        return AP_OK;
-    }
-    if (pl.small) {
-        snprintf(buf, buflen, "SmallCfg<%d, %d>", d->stride, d->Cout);
-        return AP_OK;
-    }
-    if (pl.head) {
-        snprintf(buf, buflen, "HeadCfg<%d>", d->KH);
-        return AP_OK;
-    }
-    if (pl.tsmall) {
-        snprintf(buf, buflen, "TSmallCfg<%d>", d->Cout);
-        return AP_OK;
-    }
-    if (pl.bf3) {
-        snprintf(buf, buflen, "%s%s", pl.bk->name, d->precision == AP_PRECISION_BF16 ? " bf16" : "");
-        return AP_OK;
-    }
-    snprintf(buf, buflen, "ConvCfg<%d, %d, %d, %d, %d, %d, %d>", pl.k->CI, pl.k->S, pl.k->K, pl.k->WCO, pl.k->MT,
-             pl.k->WPX, pl.k->NT);
+    if (pl.direct_cop) snprintf(buf, buflen, "DirectCfg<%d, %d>", d->KH, pl.direct_cop);
+    else if (pl.small) snprintf(buf, buflen, "SmallCfg<%d, %d>", d->stride, d->Cout);
+    else if (pl.head) snprintf(buf, buflen, "HeadCfg<%d>", d->KH);
+    else if (pl.tsmall) snprintf(buf, buflen, "TSmallCfg<%d>", d->Cout);
+    else if (pl.bf3) snprintf(buf, buflen, "%s%s", pl.bk->name, d->precision == AP_PRECISION_BF16 ? " bf16" : "");
+    else snprintf(buf, buflen, "ConvCfg<%d, %d, %d, %d, %d, %d, %d>", pl.k->CI, pl.k->S, pl.k->K, pl.k->WCO, pl.k->MT, pl.k->WPX, pl.k->NT);
     return AP_OK;
 }
 
@@ -790,21 +796,11 @@ int ap_conv2d_pack_run(const void* entries_dev, int32_t count, ap_stream_t strea
     return check_launch("pack_bf16x3_table_kernel");
 }
 
-static int conv2d_fwd_impl(const ap_conv_desc* d, const ap_out_view* view, const float* packed, const float* bias, float* y,
-                           float* stat_partials, ap_stream_t stream, bool octet = false, const ap_fused_norm* fn = nullptr,
-                           bool ob16 = false);
+}  // extern "C"
 
-int ap_conv2d_fwd(const ap_conv_desc* d, const float* packed, const float* bias, float* y,
-                  float* stat_partials, ap_stream_t stream) {
-    return conv2d_fwd_impl(d, nullptr, packed, bias, y, stat_partials, stream);
-}
+namespace apamd {
 
-int ap_conv2d_fwd_view(const ap_conv_desc* d, const ap_out_view* view, const float* packed, const float* bias, float* y,
-                       ap_stream_t stream) {
-    if (!view) return fail(AP_ERR_INVALID, "conv2d_fwd_view: null view");
-    return conv2d_fwd_impl(d, view, packed, bias, y, nullptr, stream);
-}
-
+// ------------------------------------------------------------------ which plans take which output form
 // the channel-octet output form exists in the run-time-tap and row families of the split-bf16 kernel (conv_bf16x3.h epilogue)
 static bool octet_plan_ok(const ap_conv_desc* d, const Plan& pl) {
     if (!pl.bf3 || pl.fused_phases || pl.ph4 || pl.launches.size() != 1 || (d->Cout & 7)) return false;
@@ -812,38 +808,10 @@ static bool octet_plan_ok(const ap_conv_desc* d, const Plan& pl) {
     return kern && (kern->K == 0 || kern->ROW || (kern->K == 3 && kern->S == 1 && d->precision == AP_PRECISION_BF16X3));
 }
 
-int32_t ap_conv2d_octet_ok(const ap_conv_desc* d) {
-    Plan pl;
-    if (make_plan(d, pl)) return 0;
-    return octet_plan_ok(d, pl) ? 1 : 0;
-}
-
-int ap_conv2d_fwd_octet(const ap_conv_desc* d, const float* packed, const float* bias, float* y, float* stat_partials,
-                        ap_stream_t stream) {
-    return conv2d_fwd_impl(d, nullptr, packed, bias, y, stat_partials, stream, true);
-}
-
 // the bf16-output form exists for the plain-bf16 instantiations of the dense 3x3 stride-1 tiles (Bf3Cfg::OB16)
 static bool ob16_plan_ok(const ap_conv_desc* d, const Plan& pl) {
     if (!pl.bf3 || pl.fused_phases || pl.ph4 || pl.launches.size() != 1 || d->precision != AP_PRECISION_BF16) return false;
     return pl.bk && pl.bk->fn1_ob16 != nullptr;
-}
-
-int32_t ap_conv2d_bf16out_ok(const ap_conv_desc* d) {
-    Plan pl;
-    if (make_plan(d, pl)) return 0;
-    return ob16_plan_ok(d, pl) ? 1 : 0;
-}
-
-int ap_conv2d_fwd_bf16out(const ap_conv_desc* d, const float* packed, const float* bias, void* y_bf16, float* stat_partials,
-                          ap_stream_t stream) {
-    return conv2d_fwd_impl(d, nullptr, packed, bias, reinterpret_cast<float*>(y_bf16), stat_partials, stream, false, nullptr, true);
-}
-
-int ap_conv2d_fwd_view_bf16out(const ap_conv_desc* d, const ap_out_view* view, const float* packed, const float* bias, void* y_bf16,
-                               ap_stream_t stream) {
-    if (!view) return fail(AP_ERR_INVALID, "conv2d_fwd_view_bf16out: null view");
-    return conv2d_fwd_impl(d, view, packed, bias, reinterpret_cast<float*>(y_bf16), nullptr, stream, false, nullptr, true);
 }
 
 // ---- convolution + InstanceNorm in one launch (conv_bf16x3<..., FNORM>): which plans qualify, and is the launch deadlock-free?
@@ -883,44 +851,42 @@ static bool fnorm_plan_ok(const ap_conv_desc* d, const Plan& pl) {
     return true;
 }
 
-int32_t ap_conv2d_fused_norm_ok(const ap_conv_desc* d) {
+// the answer of an ap_conv2d_*_ok query: the descriptor has a plan and the plan passes the predicate
+static int32_t plan_passes(const ap_conv_desc* d, bool (*ok)(const ap_conv_desc*, const Plan&)) {
     Plan pl;
-    if (make_plan(d, pl)) return 0;
-    return fnorm_plan_ok(d, pl) ? 1 : 0;
+    return !make_plan(d, pl) && ok(d, pl) ? 1 : 0;
 }
 
-int32_t ap_conv2d_fused_norm_counters(const ap_conv_desc* d) {
-    Plan pl;
-    int rc = make_plan(d, pl);
-    return rc ? rc : d->N * pl.co_tiles * 2 + 1;        // + the launch's error flag (set when a workgroup gave up waiting)
-}
+// ------------------------------------------------------------------ the forward launch
+// How the result is stored; the default is the whole NCHW fp32 tensor.
+struct OutForm {
+    const ap_out_view* view = nullptr;   // a window of the output, with the caller's strides
+    bool octet = false;                  // channel-octet layout y[n][Cout/8][OH*OW][8]
+    bool bf16 = false;                   // bf16 values
+    const ap_fused_norm* fn = nullptr;   // InstanceNorm of the output inside the epilogue (y is then the exchange buffer)
+};
 
-int ap_conv2d_fwd_norm(const ap_conv_desc* d, const float* packed, const ap_fused_norm* fn, ap_stream_t stream) {
-    if (!fn || !fn->partials || !fn->counters || !fn->mean || !fn->rstd) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: null workspace");
-    if (!fn->xs && !fn->y_oct) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: neither a split nor a channel-octet output");
-    if (fn->res_oct && fn->res_nchw) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: two residuals");
-    if (fn->act < 0 || fn->act > 2) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: act %d", fn->act);
-    return conv2d_fwd_impl(d, nullptr, packed, nullptr, fn->partials, fn->partials, stream, false, fn);
-}
+struct FwdArgs {
+    const float *packed, *bias;
+    float *y, *stats;    // stats: per-tile partial sums for the consumer's InstanceNorm, or null
+    hipStream_t stream;
+};
 
-static int conv2d_fwd_impl(const ap_conv_desc* d, const ap_out_view* view, const float* packed, const float* bias, float* y,
-                           float* stat_partials, ap_stream_t stream, bool octet, const ap_fused_norm* fn, bool ob16) {
-    Plan pl;
-    int rc = make_plan(d, pl);
-    if (rc) return rc;
-    if (ob16 && (!ob16_plan_ok(d, pl) || octet || fn))
+// Every refusal that depends on the arguments, before anything is launched; callers tell the refusals apart, so the order stays
+static int check_fwd_args(const ap_conv_desc* d, const Plan& pl, const OutForm& o, const FwdArgs& a) {
+    if (o.bf16 && (!ob16_plan_ok(d, pl) || o.octet || o.fn))
         return fail(AP_ERR_UNSUPPORTED, "conv2d_fwd_bf16out: only the plain-bf16 dense 3x3 stride-1 layers store bf16 (ap_conv2d_bf16out_ok)");
-    if (fn && !fnorm_plan_ok(d, pl))
+    if (o.fn && !fnorm_plan_ok(d, pl))
         return fail(AP_ERR_UNSUPPORTED, "conv2d_fwd_norm: this layer / shape cannot normalise in its epilogue (ap_conv2d_fused_norm_ok)");
-    if (!packed || !y) return fail(AP_ERR_INVALID, "null packed/y pointer");
-    if (octet && !octet_plan_ok(d, pl))
+    if (!a.packed || !a.y) return fail(AP_ERR_INVALID, "null packed/y pointer");
+    if (o.octet && !octet_plan_ok(d, pl))
         return fail(AP_ERR_UNSUPPORTED, "conv2d_fwd_octet: only single-launch split-bf16 layers of the run-time-tap / row kernel "
                                         "families with Cout %% 8 == 0 write the channel-octet layout (ap_conv2d_octet_ok)");
-    if (view) {
+    if (o.view) {
         if (!pl.bf3 || pl.fused_phases || pl.launches.size() != 1)
             return fail(AP_ERR_UNSUPPORTED, "conv2d_fwd_view: only single-launch split-bf16 plans take an output window");
-        if (view->OH < 1 || view->OW < 1 || view->OH > pl.Hout || view->OW > pl.Wout)
-            return fail(AP_ERR_INVALID, "conv2d_fwd_view: window %dx%d outside the %dx%d output", view->OH, view->OW, pl.Hout, pl.Wout);
+        if (o.view->OH < 1 || o.view->OW < 1 || o.view->OH > pl.Hout || o.view->OW > pl.Wout)
+            return fail(AP_ERR_INVALID, "conv2d_fwd_view: window %dx%d outside the %dx%d output", o.view->OH, o.view->OW, pl.Hout, pl.Wout);
     }
     if (d->presplit && !pl.bf3) return fail(AP_ERR_INVALID, "desc.presplit set for a layer that does not take split sources");
     for (int s = 0; s < d->nsrc; ++s) {
@@ -929,297 +895,359 @@ static int conv2d_fwd_impl(const ap_conv_desc* d, const ap_out_view* view, const
             return fail(AP_ERR_INVALID, "segment %d: mean and rstd must be given together", s);
         if (d->src[s].act < 0 || d->src[s].act > 2) return fail(AP_ERR_INVALID, "segment %d: act %d", s, d->src[s].act);
     }
-    if (pl.tsmall && !stat_partials) {
-        TSmallParams p;
-        memset(&p, 0, sizeof(p));
-        p.src.data = d->src[0].data; p.src.mean = d->src[0].mean; p.src.rstd = d->src[0].rstd;
-        p.src.C = d->src[0].C; p.src.act = d->src[0].act;
-        p.N = d->N; p.C = pl.Cin; p.H = d->H; p.W = d->W; p.Cout = d->Cout;
-        p.w = packed + pl.head_w_off; p.bias = bias; p.act = d->act; p.y = y;
-        if (d->N > 65535 || (d->H + 7) / 8 > 65535) return fail(AP_ERR_UNSUPPORTED, "conv_tsmall: grid too large");
-        const dim3 grid((d->W + 31) / 32, (d->H + 7) / 8, d->N);
-        if (d->Cout == 1) hipLaunchKernelGGL((conv_tsmall_f32<1>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else if (d->Cout == 2) hipLaunchKernelGGL((conv_tsmall_f32<2>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((conv_tsmall_f32<4>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        return check_launch("conv_tsmall_f32");
+    return AP_OK;
+}
+
+static int launch_tsmall(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+    TSmallParams p;
+    memset(&p, 0, sizeof(p));
+    fill_seg(p.src, d->src[0], 0);
+    p.N = d->N; p.C = pl.Cin; p.H = d->H; p.W = d->W; p.Cout = d->Cout;
+    p.w = a.packed + pl.head_w_off; p.bias = a.bias; p.act = d->act; p.y = a.y;
+    if (d->N > 65535 || (d->H + 7) / 8 > 65535) return fail(AP_ERR_UNSUPPORTED, "conv_tsmall: grid too large");
+    const dim3 grid((d->W + 31) / 32, (d->H + 7) / 8, d->N);
+    if (d->Cout == 1) hipLaunchKernelGGL((conv_tsmall_f32<1>), grid, dim3(256), 0, a.stream, p);
+    else if (d->Cout == 2) hipLaunchKernelGGL((conv_tsmall_f32<2>), grid, dim3(256), 0, a.stream, p);
+    else hipLaunchKernelGGL((conv_tsmall_f32<4>), grid, dim3(256), 0, a.stream, p);
+    return check_launch("conv_tsmall_f32");
+}
+
+// Rows per workgroup of the head kernel.  The kernel is bound by its vector ALUs (normalisation, activation, three wave shifts and
+// 16 FMAs per staged row element, on RB + 3 rows for RB outputs) and a launch is a few hundred 1024-thread workgroups: what counts
+// is the number of workgroup ROUNDS on the CUs times the rows a workgroup stages.  (Round 6; before: 3-row bands unless taller
+// ones still gave >= 200 workgroups -- 320 workgroups = two rounds at 2B = 32, 160 = 5/8 of the chip at B = 16.)
+static int launch_head(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+    const int cus = num_cus();
+    int rb = 3;
+    long long best_cost = -1;
+    for (int cand : {2, 3, 4, 5, 6, 10}) {
+        const long long wgs = (long long)d->N * ((pl.Hout + cand - 1) / cand);
+        const long long cost = ((wgs + cus - 1) / cus) * (cand + 3);
+        if (best_cost < 0 || cost < best_cost) { rb = cand; best_cost = cost; }
     }
-    if (pl.head && !stat_partials) {      // (with a statistics epilogue wanted the layer stays on the general kernel)
-        HeadParams p;
-        memset(&p, 0, sizeof(p));
-        p.src.data = d->src[0].data; p.src.mean = d->src[0].mean; p.src.rstd = d->src[0].rstd;
-        p.src.C = d->src[0].C; p.src.act = d->src[0].act;
-        p.N = d->N; p.C = pl.Cin; p.H = d->H; p.W = d->W; p.OH = pl.Hout; p.OW = pl.Wout;
-        p.w = packed + pl.head_w_off; p.bias = bias; p.act = d->act; p.y = y;
-        // Rows per workgroup.  The kernel is bound by its vector ALUs (normalisation, activation, three wave shifts and 16 FMAs per
-        // staged row element, on RB + 3 rows for RB outputs) and a launch is a few hundred 1024-thread workgroups: what counts is
-        // the number of workgroup ROUNDS on the CUs times the rows a workgroup stages.  (Round 6; before: 3-row bands unless taller
-        // ones still gave >= 200 workgroups -- 320 workgroups = two rounds at 2B = 32, 160 = 5/8 of the chip at B = 16.)
-        const int cus = num_cus();
-        int best = 3;
-        long long best_cost = -1;
-        for (int rb : {2, 3, 4, 5, 6, 10}) {
-            const long long wgs = (long long)d->N * ((pl.Hout + rb - 1) / rb);
-            const long long cost = ((wgs + cus - 1) / cus) * (rb + 3);
-            if (best_cost < 0 || cost < best_cost) { best = rb; best_cost = cost; }
-        }
-        const dim3 hg(d->N, (pl.Hout + best - 1) / best);
-        switch (best) {
-            case 2: hipLaunchKernelGGL(conv_head_fwd_kernel<2>, hg, dim3(1024), 0, (hipStream_t)stream, p); break;
-            case 4: hipLaunchKernelGGL(conv_head_fwd_kernel<4>, hg, dim3(1024), 0, (hipStream_t)stream, p); break;
-            case 5: hipLaunchKernelGGL(conv_head_fwd_kernel<5>, hg, dim3(1024), 0, (hipStream_t)stream, p); break;
-            case 6: hipLaunchKernelGGL(conv_head_fwd_kernel<6>, hg, dim3(1024), 0, (hipStream_t)stream, p); break;
-            case 10: hipLaunchKernelGGL(conv_head_fwd_kernel<10>, hg, dim3(1024), 0, (hipStream_t)stream, p); break;
-            default: hipLaunchKernelGGL(conv_head_fwd_kernel<3>, hg, dim3(1024), 0, (hipStream_t)stream, p); break;
-        }
-        return check_launch("conv_head_fwd_kernel");
+    HeadParams p;
+    memset(&p, 0, sizeof(p));
+    fill_seg(p.src, d->src[0], 0);
+    p.N = d->N; p.C = pl.Cin; p.H = d->H; p.W = d->W; p.OH = pl.Hout; p.OW = pl.Wout;
+    p.w = a.packed + pl.head_w_off; p.bias = a.bias; p.act = d->act; p.y = a.y;
+    const dim3 hg(d->N, (pl.Hout + rb - 1) / rb);
+    switch (rb) {
+        case 2: hipLaunchKernelGGL(conv_head_fwd_kernel<2>, hg, dim3(1024), 0, a.stream, p); break;
+        case 4: hipLaunchKernelGGL(conv_head_fwd_kernel<4>, hg, dim3(1024), 0, a.stream, p); break;
+        case 5: hipLaunchKernelGGL(conv_head_fwd_kernel<5>, hg, dim3(1024), 0, a.stream, p); break;
+        case 6: hipLaunchKernelGGL(conv_head_fwd_kernel<6>, hg, dim3(1024), 0, a.stream, p); break;
+        case 10: hipLaunchKernelGGL(conv_head_fwd_kernel<10>, hg, dim3(1024), 0, a.stream, p); break;
+        default: hipLaunchKernelGGL(conv_head_fwd_kernel<3>, hg, dim3(1024), 0, a.stream, p); break;
     }
-    if (pl.small) {
-        SmallKParams p;
-        memset(&p, 0, sizeof(p));
-        p.src.data = d->src[0].data; p.src.mean = d->src[0].mean; p.src.rstd = d->src[0].rstd;
-        p.src.C = d->src[0].C; p.src.act = d->src[0].act;
-        p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = pl.Cin; p.Cout = d->Cout; p.OH = pl.Hout; p.OW = pl.Wout;
-        p.pad = d->pad; p.pad_mode = d->pad_mode;
-        p.y = y; p.w = packed; p.bias = bias; p.act = d->act;
-        p.stats = stat_partials; p.stat_tiles = pl.stat_tiles;
-        p.tiles_x = (pl.Wout + 31) / 32; p.tiles_y = (pl.Hout + 7) / 8;
-        const dim3 grid((unsigned)((long long)d->N * p.tiles_y * p.tiles_x));
-        if (d->stride == 1 && d->Cout == 8) hipLaunchKernelGGL((conv_small_f32<SmallCfg<1, 8>>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else if (d->stride == 1) hipLaunchKernelGGL((conv_small_f32<SmallCfg<1, 16>>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else if (d->Cout == 8) hipLaunchKernelGGL((conv_small_gather_f32<SmallCfg<2, 8>>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((conv_small_gather_f32<SmallCfg<2, 16>>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        return check_launch("conv_small_f32");
-    }
-    if (pl.bf3) {
-        if (!d->presplit)
-            return fail(AP_ERR_INVALID, "this layer runs on the split-bf16 path: pass sources prepared by "
-                                        "ap_split_prepass and set desc.presplit (see ap_conv2d_wants_presplit)");
-        for (const auto& L : pl.launches) {
-            const Bf3Kernel* kern = pl.ph4 ? pl.bk : bf3_for_taps(pl.bk, (int)L.taps.size());
-            if (!kern) return fail(AP_ERR_UNSUPPORTED, "no split-bf16 kernel for a phase with %d taps", (int)L.taps.size());
-            const void* kfn = ob16 ? kern->fn1_ob16 : kern->kernel(d->precision);
-            rc = ensure_lds_attr(kfn);
-            if (rc) return rc;
-            ConvKParams p;
-            memset(&p, 0, sizeof(p));
-            p.nseg = d->nsrc;
-            for (int s = 0; s < d->nsrc; ++s) {
-                p.seg[s].data = d->src[s].data; p.seg[s].C = d->src[s].C; p.seg[s].chunk_begin = pl.chunk_begin[s];
-            }
-            p.N = d->N; p.H = d->H; p.W = d->W; p.Cout = d->Cout;
-            p.OH = L.OH; p.OW = L.OW; p.dy0 = L.dy0; p.dx0 = L.dx0;
-            p.pad_mode = d->pad_mode;
-            p.y = y;
-            p.o_nstride = (long long)d->Cout * pl.Hout * pl.Wout;
-            p.o_cstride = (long long)pl.Hout * pl.Wout;
-            p.o_rstride = pl.Wout;
-            p.osy = L.osy; p.osx = L.osx; p.oy_off = L.oy_off; p.ox_off = L.ox_off;
-            p.wp = packed + L.wp_off; p.bias = bias; p.act = d->act;
-            p.stats = stat_partials; p.stat_tiles = pl.stat_tiles; p.stat_tile_off = L.stat_tile_off;
-            p.ntaps = (int)L.taps.size(); p.nchunks = pl.nchunks;
-            p.tiles_x = L.tiles_x; p.tiles_y = L.tiles_y; p.co_tiles = pl.co_tiles;
-            p.cin_pad = pl.cin_pad;
-            p.wfloats = pl.bk->wfloats(p.ntaps);
-#ifdef APAMD_ABLATION
-            p.ablate = env_int("APAMD_ABLATE", 0);
-#endif
-            p.o_octet = octet ? 1 : 0;
-            if (view) {
-                // output window: a sub-grid of the output, stored with the caller's strides (ap_out_view)
-                p.OH = view->OH; p.OW = view->OW;
-                p.tiles_x = (view->OW + 31) / 32;
-                p.tiles_y = (view->OH + pl.bk->TH - 1) / pl.bk->TH;
-                p.o_nstride = view->nstride; p.o_cstride = view->cstride; p.o_rstride = view->rstride;
-                p.osy = 1; p.oy_off = view->y_off;
-                p.osx = view->xstride; p.ox_off = view->x_off * view->xstride;
-            }
-            if (pl.fused_phases) {
-                // this launch (the geometry of phase 0, shared by all) covers the four phases: their weight blocks
-                // follow each other in the packed image, so the virtual cout tile indexes them directly
-                p.nphase = 4;
-                p.co_tiles_phase = pl.co_tiles;
-                p.co_tiles = 4 * pl.co_tiles;
-                for (int ph = 0; ph < 4; ++ph) {
-                    const Launch& Lp = pl.launches[ph];
-                    p.ph_dy0[ph] = Lp.dy0; p.ph_dx0[ph] = Lp.dx0; p.ph_oy[ph] = Lp.oy_off; p.ph_ox[ph] = Lp.ox_off;
-                    p.ph_stat[ph] = Lp.stat_tile_off;
-                    p.ph_tapmask[ph] = 0;
-                    for (size_t t = 0; t < Lp.taps.size() && t < 4; ++t)
-                        if (Lp.taps[t].ky >= 0) p.ph_tapmask[ph] |= 1u << t;
-                }
-                if (pl.ph4) {
-                    // conv_ph4 walks cout tiles only and derives the phase geometry from K: check the plan agrees
-                    if (view) return fail(AP_ERR_UNSUPPORTED, "conv_ph4: output views are not supported");
-                    // (the kernel folds the phase into 32-bit per-lane byte offsets of the packed weights)
-                    if (3LL * pl.co_tiles * pl.nchunks * p.wfloats * 4 >= (1LL << 31))
-                        return fail(AP_ERR_UNSUPPORTED, "conv_ph4: packed phase blocks of %d cout tiles x %d chunks are too large", pl.co_tiles, pl.nchunks);
-                    p.co_tiles = pl.co_tiles;
-                    const int base = pl.ph4 == 3 ? 0 : -1;
-                    for (int ph = 0; ph < 4; ++ph) {
-                        const Launch& Lp = pl.launches[ph];
-                        const unsigned want = ((pl.ph4 == 3 && !(ph >> 1)) ? 1u : 3u) * 1u;          // taps along y
-                        const unsigned wanx = (pl.ph4 == 3 && !(ph & 1)) ? 1u : 3u;
-                        unsigned m = 0;
-                        for (int t = 0; t < 4; ++t) if (((want >> (t >> 1)) & 1u) && ((wanx >> (t & 1)) & 1u)) m |= 1u << t;
-                        const int oy = pl.ph4 == 3 ? 0 : (ph >> 1), ox = pl.ph4 == 3 ? 0 : (ph & 1);
-                        unsigned have = 0;
-                        for (size_t t = 0; t < Lp.taps.size() && t < 4; ++t) if (Lp.taps[t].ky >= 0) have |= 1u << t;
-                        if (have != m || Lp.dy0 != base + oy || Lp.dx0 != base + ox || Lp.oy_off != (ph >> 1) || Lp.ox_off != (ph & 1) ||
-                            Lp.osy != 2 || Lp.osx != 2 || Lp.OH != pl.launches[0].OH || Lp.OW != pl.launches[0].OW)
-                            return fail(AP_ERR_UNSUPPORTED, "conv_ph4: phase %d geometry (taps %x/%x, origin %d,%d)", ph, have, m, Lp.dy0, Lp.dx0);
-                    }
-                }
-            }
-            p.tap_bits = 0;
-            if (d->s2d_k == 3 && !d->transposed && pl.bk->K == 0 && d->KW == 2 && d->nsrc == 1 && d->src[0].C % 64 == 0) {
-                // space-to-depth form of a 3x3 stride-2 layer: input phase (ry, rx) = 16-channel chunks [r C/16, (r+1) C/16)
-                p.s2d_div = d->src[0].C / 64;
-                for (int r = 0; r < 4; ++r) {
-                    p.s2d_mask[r] = 0;
-                    for (int t = 0; t < 4; ++t)
-                        if (2 * (t >> 1) + (r >> 1) <= 2 && 2 * (t & 1) + (r & 1) <= 2) p.s2d_mask[r] |= 1u << t;
-                }
-            }
-            if (pl.bk->K == 0) {
-                if (p.ntaps > 4) return fail(AP_ERR_UNSUPPORTED, "phase with %d taps", p.ntaps);
-                for (int t = 0; t < p.ntaps; ++t)
-                    p.tap_bits |= (unsigned)((L.taps[t].ly & 1) | ((L.taps[t].lx & 1) << 1)) << (2 * t);
-            }
-            if (p.s2d_div > 0 && (p.s2d_div & 1) == 0 && p.nchunks == 4 * p.s2d_div && kern->kernel_s2d3(d->precision)) {
-                // even chunk count per input phase: the instantiation with compile-time tap sets (no fragment reads for absent taps)
-                kfn = kern->kernel_s2d3(d->precision);
-                rc = ensure_lds_attr(kfn);
-                if (rc) return rc;
-            }
-            if (fn) {
-                kfn = bf3_fnorm_kernel();
-                rc = ensure_lds_attr(kfn);
-                if (rc) return rc;
-                p.fn_act = fn->act; p.fn_eps = fn->eps; p.fn_inv_count = 1.0 / ((double)pl.Hout * pl.Wout);
-                p.fn_res_oct = fn->res_oct; p.fn_res_nchw = fn->res_nchw; p.fn_y_oct = fn->y_oct; p.fn_xs = fn->xs;
-                p.fn_mean = fn->mean; p.fn_rstd = fn->rstd; p.fn_counters = fn->counters;
-                p.fn_debug = env_int("APAMD_FNORM_DEBUG", 0);
-            }
-            size_t lds = kern->lds(d->precision, p.ntaps);
-            bool sb = false;
-#ifdef APAMD_VARIANTS
-            if (!fn && !view && !octet && kern->K == 3 && kern->S == 1 && kern->TH == 16 && !kern->ROW && d->precision != AP_PRECISION_BF16 &&
-                p.osx == 1 && p.osy == 1 && p.oy_off == 0 && p.ox_off == 0 && env_int("APAMD_CONV_SB", 0)) {
-                // rejected experiment kept for A/B (tools/variants/conv_bf16x3_sb.h, `make variants`): one LDS stage per
-                // workgroup, two workgroups per CU
-                kfn = bf3_sb_kernel(&lds);
-                rc = ensure_lds_attr(kfn);
-                if (rc) return rc;
-                p.fn_debug = env_int("APAMD_CONV_SB_SKEW", 0);
-                sb = true;
-            }
-#endif
-#ifdef APAMD_ABLATION
-            // cycle account (tools/cycle_account.py): APAMD_STAMP_BUF = device address of the stamp buffer, APAMD_STAMP_WORDS =
-            // dwords per wave; the stamps live in LDS behind the stage buffers, so only kernels that leave that room take them
-            if (const char* sb_ = getenv("APAMD_STAMP_BUF")) {
-                const int words = env_int("APAMD_STAMP_WORDS", 512);
-                if (!pl.ph4 && lds + (size_t)16 * words <= 160 * 1024) {
-                    p.stamps = reinterpret_cast<unsigned*>(strtoull(sb_, nullptr, 0));
-                    p.stamp_lds_off = (int)lds;
-                    p.stamp_words = words;
-                    lds += (size_t)16 * words;
-                }
-            }
-#endif
-            if (lds > 160 * 1024) return fail(AP_ERR_UNSUPPORTED, "bf16x3 LDS tile of %zu bytes does not fit", lds);
-            if (p.nchunks < 2) return fail(AP_ERR_UNSUPPORTED, "bf16x3 pipeline needs >= 32 input channels");
-            if (((long long)d->H * d->W + 1) * 32 >= (1LL << 31))   // per-lane DMA offsets span two channel-group planes
-                return fail(AP_ERR_UNSUPPORTED, "split-bf16 path: %d x %d planes are too large", d->H, d->W);
-            // persistent workgroups: one per CU (the two LDS stages fill a CU), each walks its share of the tiles
-            long long nblk = (long long)d->N * p.tiles_y * p.tiles_x * p.co_tiles;
-            // (two per CU when two stage sets fit its 160 KB of LDS)
-            int cus = num_cus() * ((2 * lds <= 160 * 1024 || sb) ? 2 : 1);
-            if (const int forced = env_int("APAMD_BF3_BLOCKS", 0)) {      // tuning / test knob: never silent
-                static bool told = false;
-                if (!told) fprintf(stderr, "libapamd: APAMD_BF3_BLOCKS=%d overrides the persistent workgroup count\n", forced);
-                told = true;
-                cus = forced;
-            }
-            if (nblk > cus) nblk = cus;
-            void* args[] = {&p};
-            hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)nblk), dim3(256), args, lds, (hipStream_t)stream);
-            if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "conv_bf16x3 launch: %s", hipGetErrorString(e));
-            if (pl.fused_phases) break;
-        }
-        return AP_OK;
-    }
-    rc = ensure_lds_attr(pl.direct_cop ? direct_fn(d->KH, pl.direct_cop) : pl.k->fn);
+    return check_launch("conv_head_fwd_kernel");
+}
+
+static int launch_small(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+    SmallKParams p;
+    memset(&p, 0, sizeof(p));
+    fill_seg(p.src, d->src[0], 0);
+    p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = pl.Cin; p.Cout = d->Cout; p.OH = pl.Hout; p.OW = pl.Wout;
+    p.pad = d->pad; p.pad_mode = d->pad_mode;
+    p.y = a.y; p.w = a.packed; p.bias = a.bias; p.act = d->act;
+    p.stats = a.stats; p.stat_tiles = pl.stat_tiles;
+    p.tiles_x = (pl.Wout + 31) / 32; p.tiles_y = (pl.Hout + 7) / 8;
+    const dim3 grid((unsigned)((long long)d->N * p.tiles_y * p.tiles_x));
+    if (d->stride == 1 && d->Cout == 8) hipLaunchKernelGGL((conv_small_f32<SmallCfg<1, 8>>), grid, dim3(256), 0, a.stream, p);
+    else if (d->stride == 1) hipLaunchKernelGGL((conv_small_f32<SmallCfg<1, 16>>), grid, dim3(256), 0, a.stream, p);
+    else if (d->Cout == 8) hipLaunchKernelGGL((conv_small_gather_f32<SmallCfg<2, 8>>), grid, dim3(256), 0, a.stream, p);
+    else hipLaunchKernelGGL((conv_small_gather_f32<SmallCfg<2, 16>>), grid, dim3(256), 0, a.stream, p);
+    return check_launch("conv_small_f32");
+}
+
+static int launch_direct(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+    const void* kfn = direct_fn(d->KH, pl.direct_cop);
+    int rc = ensure_lds_attr(kfn);
     if (rc) return rc;
-    if (pl.direct_cop) {
-        DirectKParams p;
-        memset(&p, 0, sizeof(p));
-        p.nseg = d->nsrc;
-        for (int s = 0; s < d->nsrc; ++s) {
-            p.seg[s].data = d->src[s].data; p.seg[s].mean = d->src[s].mean; p.seg[s].rstd = d->src[s].rstd;
-            p.seg[s].C = d->src[s].C; p.seg[s].act = d->src[s].act; p.seg[s].chunk_begin = pl.chunk_begin[s];
-        }
-        p.N = d->N; p.H = d->H; p.W = d->W; p.Cout = d->Cout; p.OH = pl.Hout; p.OW = pl.Wout;
-        p.pad = d->pad; p.pad_mode = d->pad_mode;
-        p.y = y; p.wp = packed; p.bias = bias; p.act = d->act;
-        p.stats = stat_partials; p.stat_tiles = pl.stat_tiles;
-        p.nchunks = pl.nchunks; p.cin_pad = pl.cin_pad;
-        p.tiles_x = (pl.Wout + 63) / 64; p.tiles_y = (pl.Hout + 15) / 16;
-        const size_t lds = direct_lds_bytes(d->KH, pl.direct_cop, p.nchunks > 1 ? 2 : 1, p.cin_pad);
-        void* args[] = {&p};
-        hipError_t e = hipLaunchKernel(direct_fn(d->KH, pl.direct_cop), dim3((unsigned)(d->N * p.tiles_y * p.tiles_x)),
-                                       dim3(256), args, lds, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "conv_direct_f32 launch: %s", hipGetErrorString(e));
-        return AP_OK;
-    }
-    for (const auto& L : pl.launches) {
-        ConvKParams p;
-        memset(&p, 0, sizeof(p));
-        p.nseg = d->nsrc;
-        for (int s = 0; s < d->nsrc; ++s) {
-            p.seg[s].data = d->src[s].data;
-            p.seg[s].mean = d->src[s].mean;
-            p.seg[s].rstd = d->src[s].rstd;
-            p.seg[s].C = d->src[s].C;
-            p.seg[s].act = d->src[s].act;
-            p.seg[s].chunk_begin = pl.chunk_begin[s];
-        }
-        p.N = d->N; p.H = d->H; p.W = d->W; p.Cout = d->Cout;
-        p.OH = L.OH; p.OW = L.OW; p.dy0 = L.dy0; p.dx0 = L.dx0;
-        p.pad_mode = d->pad_mode;
-        p.y = y;
-        p.o_nstride = (long long)d->Cout * pl.Hout * pl.Wout;
-        p.o_cstride = (long long)pl.Hout * pl.Wout;
-        p.o_rstride = pl.Wout;
-        p.osy = L.osy; p.osx = L.osx; p.oy_off = L.oy_off; p.ox_off = L.ox_off;
-        p.wp = packed + L.wp_off;
-        p.bias = bias;
-        p.act = d->act;
-        p.stats = stat_partials;
-        p.stat_tiles = pl.stat_tiles;
-        p.stat_tile_off = L.stat_tile_off;
-        p.ntaps = (int)L.taps.size();
-        p.nchunks = pl.nchunks;
-        p.tiles_x = L.tiles_x; p.tiles_y = L.tiles_y; p.co_tiles = pl.co_tiles;
-        p.cin_pad = pl.cin_pad;
-        p.wfloats = pl.k->wfloats(p.ntaps);
+    DirectKParams p;
+    memset(&p, 0, sizeof(p));
+    p.nseg = d->nsrc;
+    for (int s = 0; s < d->nsrc; ++s) fill_seg(p.seg[s], d->src[s], pl.chunk_begin[s]);
+    p.N = d->N; p.H = d->H; p.W = d->W; p.Cout = d->Cout; p.OH = pl.Hout; p.OW = pl.Wout;
+    p.pad = d->pad; p.pad_mode = d->pad_mode;
+    p.y = a.y; p.wp = a.packed; p.bias = a.bias; p.act = d->act;
+    p.stats = a.stats; p.stat_tiles = pl.stat_tiles;
+    p.nchunks = pl.nchunks; p.cin_pad = pl.cin_pad;
+    p.tiles_x = (pl.Wout + 63) / 64; p.tiles_y = (pl.Hout + 15) / 16;
+    const size_t lds = direct_lds_bytes(d->KH, pl.direct_cop, p.nchunks > 1 ? 2 : 1, p.cin_pad);
+    void* args[] = {&p};
+    hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)(d->N * p.tiles_y * p.tiles_x)), dim3(256), args, lds, a.stream);
+    if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "conv_direct_f32 launch: %s", hipGetErrorString(e));
+    return AP_OK;
+}
+
+// what the fp32 implicit-GEMM and the split-bf16 kernel take alike for launch L (with_norm = false: sources are split copies)
+static ConvKParams conv_params(const ap_conv_desc* d, const Plan& pl, const Launch& L, const FwdArgs& a, bool with_norm) {
+    ConvKParams p;
+    memset(&p, 0, sizeof(p));
+    p.nseg = d->nsrc;
+    for (int s = 0; s < d->nsrc; ++s) fill_seg(p.seg[s], d->src[s], pl.chunk_begin[s], with_norm);
+    p.N = d->N; p.H = d->H; p.W = d->W; p.Cout = d->Cout;
+    p.OH = L.OH; p.OW = L.OW; p.dy0 = L.dy0; p.dx0 = L.dx0;
+    p.pad_mode = d->pad_mode; p.y = a.y;
+    p.o_nstride = (long long)d->Cout * pl.Hout * pl.Wout; p.o_cstride = (long long)pl.Hout * pl.Wout; p.o_rstride = pl.Wout;
+    p.osy = L.osy; p.osx = L.osx; p.oy_off = L.oy_off; p.ox_off = L.ox_off;
+    p.wp = a.packed + L.wp_off; p.bias = a.bias; p.act = d->act;
+    p.stats = a.stats; p.stat_tiles = pl.stat_tiles; p.stat_tile_off = L.stat_tile_off;
+    p.ntaps = (int)L.taps.size(); p.nchunks = pl.nchunks;
+    p.tiles_x = L.tiles_x; p.tiles_y = L.tiles_y; p.co_tiles = pl.co_tiles;
+    p.cin_pad = pl.cin_pad;
 #ifdef APAMD_ABLATION
-        p.ablate = env_int("APAMD_ABLATE", 0);
+    p.ablate = env_int("APAMD_ABLATE", 0);
 #endif
-        p.tap_bits = 0;
-        if (pl.k->K == 0) {
-            if (p.ntaps > 4) return fail(AP_ERR_UNSUPPORTED, "phase with %d taps", p.ntaps);
-            for (int t = 0; t < p.ntaps; ++t)
-                p.tap_bits |= (unsigned)((L.taps[t].ly & 1) | ((L.taps[t].lx & 1) << 1)) << (2 * t);
-        }
+    return p;
+}
+
+// ConvKParams.tap_bits of a run-time-tap kernel (K == 0, at most 4 taps in a 2 x 2 window): bit 2t = ly, bit 2t+1 = lx of tap t
+static int tap_bits(const Launch& L, unsigned& bits) {
+    const int ntaps = (int)L.taps.size();
+    if (ntaps > 4) return fail(AP_ERR_UNSUPPORTED, "phase with %d taps", ntaps);
+    bits = 0;
+    for (int t = 0; t < ntaps; ++t) bits |= (unsigned)((L.taps[t].ly & 1) | ((L.taps[t].lx & 1) << 1)) << (2 * t);
+    return AP_OK;
+}
+
+static int launch_igemm(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+    int rc = ensure_lds_attr(pl.k->fn);
+    if (rc) return rc;
+    for (const auto& L : pl.launches) {
+        ConvKParams p = conv_params(d, pl, L, a, true);
+        p.wfloats = pl.k->wfloats(p.ntaps);
+        if (pl.k->K == 0 && (rc = tap_bits(L, p.tap_bits))) return rc;
         const size_t lds = 4 * pl.k->lds_floats(p.ntaps, p.nchunks > 1 ? 2 : 1, p.cin_pad);
         const long long nblk = (long long)d->N * L.tiles_y * L.tiles_x * pl.co_tiles;
         if (nblk > 0x7fffffffLL) return fail(AP_ERR_UNSUPPORTED, "grid too large");
         void* args[] = {&p};
-        hipError_t e = hipLaunchKernel(pl.k->fn, dim3((unsigned)nblk), dim3(256), args, lds, (hipStream_t)stream);
+        hipError_t e = hipLaunchKernel(pl.k->fn, dim3((unsigned)nblk), dim3(256), args, lds, a.stream);
         if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "conv_igemm_f32 launch: %s", hipGetErrorString(e));
     }
     return AP_OK;
+}
+
+// ---- split-bf16 launches
+// bit t of the result: tap t of the 2 x 2 window exists in this phase of a fused launch
+static unsigned phase_tapmask(const Launch& L) {
+    unsigned m = 0;
+    for (size_t t = 0; t < L.taps.size() && t < 4; ++t)
+        if (L.taps[t].ky >= 0) m |= 1u << t;
+    return m;
+}
+
+// conv_ph4 walks cout tiles only and derives the phase geometry from K: check the plan agrees
+static int check_ph4_plan(const Plan& pl, const ap_out_view* view) {
+    if (view) return fail(AP_ERR_UNSUPPORTED, "conv_ph4: output views are not supported");
+    // (the kernel folds the phase into 32-bit per-lane byte offsets of the packed weights)
+    const int wfloats = pl.bk->wfloats((int)pl.launches[0].taps.size());
+    if (3LL * pl.co_tiles * pl.nchunks * wfloats * 4 >= (1LL << 31))
+        return fail(AP_ERR_UNSUPPORTED, "conv_ph4: packed phase blocks of %d cout tiles x %d chunks are too large", pl.co_tiles, pl.nchunks);
+    const int base = pl.ph4 == 3 ? 0 : -1;
+    for (int ph = 0; ph < 4; ++ph) {
+        const Launch& Lp = pl.launches[ph];
+        const unsigned want = (pl.ph4 == 3 && !(ph >> 1)) ? 1u : 3u;          // taps along y
+        const unsigned wanx = (pl.ph4 == 3 && !(ph & 1)) ? 1u : 3u;
+        unsigned m = 0;
+        for (int t = 0; t < 4; ++t) if (((want >> (t >> 1)) & 1u) && ((wanx >> (t & 1)) & 1u)) m |= 1u << t;
+        const int oy = pl.ph4 == 3 ? 0 : (ph >> 1), ox = pl.ph4 == 3 ? 0 : (ph & 1);
+        const unsigned have = phase_tapmask(Lp);
+        if (have != m || Lp.dy0 != base + oy || Lp.dx0 != base + ox || Lp.oy_off != (ph >> 1) || Lp.ox_off != (ph & 1) ||
+            Lp.osy != 2 || Lp.osx != 2 || Lp.OH != pl.launches[0].OH || Lp.OW != pl.launches[0].OW)
+            return fail(AP_ERR_UNSUPPORTED, "conv_ph4: phase %d geometry (taps %x/%x, origin %d,%d)", ph, have, m, Lp.dy0, Lp.dx0);
+    }
+    return AP_OK;
+}
+
+// one launch (phase 0's geometry) covers the four phases: their weight blocks follow each other in the packed image, so the
+// virtual cout tile indexes them directly (conv_ph4 walks the real cout tiles)
+static void fused_phase_params(ConvKParams& p, const Plan& pl) {
+    p.nphase = 4;
+    p.co_tiles_phase = pl.co_tiles;
+    p.co_tiles = pl.ph4 ? pl.co_tiles : 4 * pl.co_tiles;
+    for (int ph = 0; ph < 4; ++ph) {
+        const Launch& Lp = pl.launches[ph];
+        p.ph_dy0[ph] = Lp.dy0; p.ph_dx0[ph] = Lp.dx0; p.ph_oy[ph] = Lp.oy_off; p.ph_ox[ph] = Lp.ox_off;
+        p.ph_stat[ph] = Lp.stat_tile_off;
+        p.ph_tapmask[ph] = phase_tapmask(Lp);
+    }
+}
+
+// space-to-depth form of a 3x3 stride-2 layer: input phase (ry, rx) = 16-channel chunks [r C/16, (r+1) C/16)
+static void s2d3_params(ConvKParams& p, const ap_conv_desc* d, const Plan& pl) {
+    if (d->s2d_k != 3 || d->transposed || pl.bk->K != 0 || d->KW != 2 || d->nsrc != 1 || d->src[0].C % 64 != 0) return;
+    p.s2d_div = d->src[0].C / 64;
+    for (int r = 0; r < 4; ++r) {
+        p.s2d_mask[r] = 0;
+        for (int t = 0; t < 4; ++t)
+            if (2 * (t >> 1) + (r >> 1) <= 2 && 2 * (t & 1) + (r & 1) <= 2) p.s2d_mask[r] |= 1u << t;
+    }
+}
+
+// persistent workgroups, each walks its share of the tiles: one per CU, two when two stage sets fit its 160 KB of LDS
+static unsigned bf3_workgroups(long long tiles, size_t lds, bool two_per_cu) {
+    int cus = num_cus() * ((2 * lds <= 160 * 1024 || two_per_cu) ? 2 : 1);
+    if (const int forced = env_int("APAMD_BF3_BLOCKS", 0)) {      // tuning / test knob: never silent
+        static bool told = false;
+        if (!told) fprintf(stderr, "libapamd: APAMD_BF3_BLOCKS=%d overrides the persistent workgroup count\n", forced);
+        told = true;
+        cus = forced;
+    }
+    return (unsigned)(tiles > cus ? cus : tiles);
+}
+
+static int launch_bf3(const ap_conv_desc* d, const Plan& pl, const OutForm& o, const FwdArgs& a) {
+    if (!d->presplit)
+        return fail(AP_ERR_INVALID, "this layer runs on the split-bf16 path: pass sources prepared by "
+                                    "ap_split_prepass and set desc.presplit (see ap_conv2d_wants_presplit)");
+    int rc = pl.ph4 ? check_ph4_plan(pl, o.view) : AP_OK;
+    if (rc) return rc;
+    for (const auto& L : pl.launches) {
+        const Bf3Kernel* kern = pl.ph4 ? pl.bk : bf3_for_taps(pl.bk, (int)L.taps.size());
+        if (!kern) return fail(AP_ERR_UNSUPPORTED, "no split-bf16 kernel for a phase with %d taps", (int)L.taps.size());
+        ConvKParams p = conv_params(d, pl, L, a, false);
+        p.wfloats = pl.bk->wfloats(p.ntaps);
+        p.o_octet = o.octet ? 1 : 0;
+        if (const ap_out_view* v = o.view) {
+            // output window: a sub-grid of the output, stored with the caller's strides (ap_out_view)
+            p.OH = v->OH; p.OW = v->OW;
+            p.tiles_x = (v->OW + 31) / 32;
+            p.tiles_y = (v->OH + pl.bk->TH - 1) / pl.bk->TH;
+            p.o_nstride = v->nstride; p.o_cstride = v->cstride; p.o_rstride = v->rstride;
+            p.osy = 1; p.oy_off = v->y_off;
+            p.osx = v->xstride; p.ox_off = v->x_off * v->xstride;
+        }
+        if (pl.fused_phases) fused_phase_params(p, pl);
+        s2d3_params(p, d, pl);
+        if (pl.bk->K == 0 && (rc = tap_bits(L, p.tap_bits))) return rc;
+        const void* kfn = o.bf16 ? kern->fn1_ob16 : kern->kernel(d->precision);
+        // even chunk count per input phase: the instantiation with compile-time tap sets (no fragment reads for absent taps)
+        if (p.s2d_div > 0 && (p.s2d_div & 1) == 0 && p.nchunks == 4 * p.s2d_div && kern->kernel_s2d3(d->precision))
+            kfn = kern->kernel_s2d3(d->precision);
+        if (const ap_fused_norm* fn = o.fn) {
+            kfn = bf3_fnorm_kernel();
+            p.fn_act = fn->act; p.fn_eps = fn->eps; p.fn_inv_count = 1.0 / ((double)pl.Hout * pl.Wout);
+            p.fn_res_oct = fn->res_oct; p.fn_res_nchw = fn->res_nchw; p.fn_y_oct = fn->y_oct; p.fn_xs = fn->xs;
+            p.fn_mean = fn->mean; p.fn_rstd = fn->rstd; p.fn_counters = fn->counters;
+            p.fn_debug = env_int("APAMD_FNORM_DEBUG", 0);
+        }
+        rc = ensure_lds_attr(kfn);
+        if (rc) return rc;
+        size_t lds = kern->lds(d->precision, p.ntaps);
+        bool sb = false;
+#ifdef APAMD_VARIANTS
+        if (!o.fn && !o.view && !o.octet && kern->K == 3 && kern->S == 1 && kern->TH == 16 && !kern->ROW && d->precision != AP_PRECISION_BF16 &&
+            p.osx == 1 && p.osy == 1 && p.oy_off == 0 && p.ox_off == 0 && env_int("APAMD_CONV_SB", 0)) {
+            // rejected experiment kept for A/B (tools/variants/conv_bf16x3_sb.h, `make variants`): one LDS stage per
+            // workgroup, two workgroups per CU
+            kfn = bf3_sb_kernel(&lds);
+            rc = ensure_lds_attr(kfn);
+            if (rc) return rc;
+            p.fn_debug = env_int("APAMD_CONV_SB_SKEW", 0);
+            sb = true;
+        }
+#endif
+#ifdef APAMD_ABLATION
+        // cycle account (tools/cycle_account.py): APAMD_STAMP_BUF = device address of the stamp buffer, APAMD_STAMP_WORDS =
+        // dwords per wave; the stamps live in LDS behind the stage buffers, so only kernels that leave that room take them
+        if (const char* sb_ = getenv("APAMD_STAMP_BUF")) {
+            const int words = env_int("APAMD_STAMP_WORDS", 512);
+            if (!pl.ph4 && lds + (size_t)16 * words <= 160 * 1024) {
+                p.stamps = reinterpret_cast<unsigned*>(strtoull(sb_, nullptr, 0));
+                p.stamp_lds_off = (int)lds;
+                p.stamp_words = words;
+                lds += (size_t)16 * words;
+            }
+        }
+#endif
+        if (lds > 160 * 1024) return fail(AP_ERR_UNSUPPORTED, "bf16x3 LDS tile of %zu bytes does not fit", lds);
+        if (p.nchunks < 2) return fail(AP_ERR_UNSUPPORTED, "bf16x3 pipeline needs >= 32 input channels");
+        if (((long long)d->H * d->W + 1) * 32 >= (1LL << 31))   // per-lane DMA offsets span two channel-group planes
+            return fail(AP_ERR_UNSUPPORTED, "split-bf16 path: %d x %d planes are too large", d->H, d->W);
+        const unsigned nblk = bf3_workgroups((long long)d->N * p.tiles_y * p.tiles_x * p.co_tiles, lds, sb);
+        void* args[] = {&p};
+        hipError_t e = hipLaunchKernel(kfn, dim3(nblk), dim3(256), args, lds, a.stream);
+        if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "conv_bf16x3 launch: %s", hipGetErrorString(e));
+        if (pl.fused_phases) break;
+    }
+    return AP_OK;
+}
+
+// Every forward entry point: plan, refuse what the plan or the arguments rule out, then the family's launcher
+static int conv2d_fwd_impl(const ap_conv_desc* d, const OutForm& o, const FwdArgs& a) {
+    Plan pl;
+    int rc = make_plan(d, pl);
+    if (rc) return rc;
+    rc = check_fwd_args(d, pl, o, a);
+    if (rc) return rc;
+    // (with a statistics epilogue wanted the two narrow-output layers stay on the general kernel)
+    if (pl.tsmall && !a.stats) return launch_tsmall(d, pl, a);
+    if (pl.head && !a.stats) return launch_head(d, pl, a);
+    if (pl.small) return launch_small(d, pl, a);
+    if (pl.bf3) return launch_bf3(d, pl, o, a);
+    if (pl.direct_cop) return launch_direct(d, pl, a);
+    return launch_igemm(d, pl, a);
+}
+
+}  // namespace apamd
+
+extern "C" {
+
+int32_t ap_conv2d_octet_ok(const ap_conv_desc* d) { return plan_passes(d, octet_plan_ok); }
+int32_t ap_conv2d_bf16out_ok(const ap_conv_desc* d) { return plan_passes(d, ob16_plan_ok); }
+int32_t ap_conv2d_fused_norm_ok(const ap_conv_desc* d) { return plan_passes(d, fnorm_plan_ok); }
+
+int32_t ap_conv2d_fused_norm_counters(const ap_conv_desc* d) {
+    Plan pl;
+    int rc = make_plan(d, pl);
+    return rc ? rc : d->N * pl.co_tiles * 2 + 1;        // + the launch's error flag (set when a workgroup gave up waiting)
+}
+
+int ap_conv2d_fwd(const ap_conv_desc* d, const float* packed, const float* bias, float* y,
+                  float* stat_partials, ap_stream_t stream) {
+    return conv2d_fwd_impl(d, OutForm(), {packed, bias, y, stat_partials, (hipStream_t)stream});
+}
+
+int ap_conv2d_fwd_view(const ap_conv_desc* d, const ap_out_view* view, const float* packed, const float* bias, float* y,
+                       ap_stream_t stream) {
+    if (!view) return fail(AP_ERR_INVALID, "conv2d_fwd_view: null view");
+    OutForm o;
+    o.view = view;
+    return conv2d_fwd_impl(d, o, {packed, bias, y, nullptr, (hipStream_t)stream});
+}
+
+int ap_conv2d_fwd_octet(const ap_conv_desc* d, const float* packed, const float* bias, float* y, float* stat_partials,
+                        ap_stream_t stream) {
+    OutForm o;
+    o.octet = true;
+    return conv2d_fwd_impl(d, o, {packed, bias, y, stat_partials, (hipStream_t)stream});
+}
+
+int ap_conv2d_fwd_bf16out(const ap_conv_desc* d, const float* packed, const float* bias, void* y_bf16, float* stat_partials,
+                          ap_stream_t stream) {
+    OutForm o;
+    o.bf16 = true;
+    return conv2d_fwd_impl(d, o, {packed, bias, reinterpret_cast<float*>(y_bf16), stat_partials, (hipStream_t)stream});
+}
+
+int ap_conv2d_fwd_view_bf16out(const ap_conv_desc* d, const ap_out_view* view, const float* packed, const float* bias, void* y_bf16,
+                               ap_stream_t stream) {
+    if (!view) return fail(AP_ERR_INVALID, "conv2d_fwd_view_bf16out: null view");
+    OutForm o;
+    o.view = view;
+    o.bf16 = true;
+    return conv2d_fwd_impl(d, o, {packed, bias, reinterpret_cast<float*>(y_bf16), nullptr, (hipStream_t)stream});
+}
+
+int ap_conv2d_fwd_norm(const ap_conv_desc* d, const float* packed, const ap_fused_norm* fn, ap_stream_t stream) {
+    if (!fn || !fn->partials || !fn->counters || !fn->mean || !fn->rstd) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: null workspace");
+    if (!fn->xs && !fn->y_oct) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: neither a split nor a channel-octet output");
+    if (fn->res_oct && fn->res_nchw) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: two residuals");
+    if (fn->act < 0 || fn->act > 2) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: act %d", fn->act);
+    OutForm o;
+    o.fn = fn;
+    return conv2d_fwd_impl(d, o, {packed, nullptr, fn->partials, fn->partials, (hipStream_t)stream});
 }
 
 }  // extern "C"

@@ -262,8 +262,7 @@ static int launch_pad(const ap_src* segs, int nseg, int N, int C, int H, int W, 
     p.nseg = nseg;
     int cbeg = 0;
     for (int s = 0; s < nseg; ++s) {
-        p.seg[s].data = segs[s].data; p.seg[s].mean = segs[s].mean; p.seg[s].rstd = segs[s].rstd;
-        p.seg[s].C = segs[s].C; p.seg[s].act = segs[s].act; p.seg[s].chunk_begin = cbeg;
+        fill_seg(p.seg[s], segs[s], cbeg);
         cbeg += segs[s].C;
     }
     p.N = N; p.C = C; p.H = H; p.W = W; p.pad = pad; p.pad_mode = pad_mode; p.Hp = Hp; p.Wp = Wp; p.out = out;
@@ -514,7 +513,7 @@ int ap_conv_head_wgrad(const ap_src* src, const float* g, int32_t N, int32_t H, 
                     kHeadMaxH, kHeadMaxW, K, pad, H, W);
     HeadParams p;
     memset(&p, 0, sizeof(p));
-    p.src.data = src->data; p.src.mean = src->mean; p.src.rstd = src->rstd; p.src.C = src->C; p.src.act = src->act;
+    fill_seg(p.src, *src, 0);
     p.N = N; p.C = src->C; p.H = H; p.W = W; p.OH = OH; p.OW = OW;
     p.g = g; p.dw = dw;
     hipLaunchKernelGGL(conv_head_wgrad_kernel, dim3(src->C), dim3(256), 0, (hipStream_t)stream, p);
@@ -550,7 +549,7 @@ int ap_conv_final_wgrad(const ap_src* src, const float* g, int32_t N, int32_t H,
     hipStream_t stream = (hipStream_t)stream_;
     WgradFinalParams p;
     memset(&p, 0, sizeof(p));
-    p.src.data = src->data; p.src.mean = src->mean; p.src.rstd = src->rstd; p.src.C = src->C; p.src.act = src->act;
+    fill_seg(p.src, *src, 0);
     p.g = g; p.N = N; p.C = src->C; p.H = H; p.W = W; p.pad_mode = pad_mode;
     int P;
     final_split(N, src->C, H, W, p.tiles_x, p.tiles_y, p.tiles_per_block, P);
@@ -845,8 +844,7 @@ static int wgrad_impl(const ap_wgrad_desc* d, const void* g_t, float* workspace,
     if (pl.narrow_cob) {
         WgradNarrowParams p;
         memset(&p, 0, sizeof(p));
-        p.src.data = d->src[0].data; p.src.mean = d->src[0].mean; p.src.rstd = d->src[0].rstd;
-        p.src.C = d->src[0].C; p.src.act = d->src[0].act;
+        fill_seg(p.src, d->src[0], 0);
         p.g = d->g.data;
         p.N = d->N; p.M = d->M; p.GH = d->GH; p.GW = d->GW; p.H = d->H; p.W = d->W; p.pad = d->pad; p.pad_mode = d->pad_mode;
         p.rows_per_block = pl.rows_per_block; p.gwc = pl.gwc; p.gwc_shift = pl.gwc_shift; p.rpi = pl.rpi;

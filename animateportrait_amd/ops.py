@@ -67,6 +67,11 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _stand_in(shape, device):
+    """A storage-less fp32 tensor that carries shape and device for a feature that has no NCHW tensor (Feat.is_split_only)."""
+    return torch.empty(1, dtype=torch.float32, device=device).expand(shape)
+
+
 def _require_device(t, name, allow_bf16=False):
     """allow_bf16: the caller's kernel also reads a tensor of bf16 values (a raw convolution output / a data gradient stored by
     ap_conv2d_fwd_bf16out in the plain-bf16 train step) and is told so; everybody else refuses one loudly."""
@@ -116,7 +121,7 @@ class Feat:
     def split_only(cls, shape, xs):
         """A feature that exists only as its split-bf16 copy (inference: the fp32 tensor is never written).
         ``data`` is a storage-less stand-in that carries shape and device; fp32 consumers reject it."""
-        f = cls(torch.empty(1, dtype=torch.float32, device=xs.device).expand(shape))
+        f = cls(_stand_in(shape, xs.device))
         f.xs = xs
         return f
 
@@ -201,10 +206,18 @@ class ConvSpec:
     def fill_sources(self, d, srcs):
         """Point the descriptor at (virtual) fp32 sources; reading mean / rstd finalises pending statistics."""
         for i, f in enumerate(srcs):
-            d.src[i].data = f.data.data_ptr()
-            d.src[i].mean = f.mean.data_ptr() if f.virtual else None
-            d.src[i].rstd = f.rstd.data_ptr() if f.virtual else None
-            d.src[i].act = f.act
+            d.src[i] = _src_of(f)
+
+    def presplit_desc(self, n, h, w, srcs=(), act=ACT_NONE, d=None):
+        """The descriptor (``d``, or a new one) of a layer on the split-bf16 path: ``presplit`` set and the sources pointed at
+        the split copies of ``srcs`` (made on first use), which carry the producers' InstanceNorm + activation already."""
+        d = self.desc(n, h, w, None, act) if d is None else d
+        d.presplit = 1
+        for i, f in enumerate(srcs):
+            d.src[i].data = presplit(f, self.precision).data_ptr()
+            d.src[i].mean = d.src[i].rstd = None
+            d.src[i].act = ACT_NONE
+        return d
 
     def out_size(self, h, w):
         d = self.desc(1, h, w)
@@ -361,6 +374,17 @@ def packed_slot(spec, weight, view, slot):
     return slot
 
 
+def _src_of(f, bf16_bit=False):
+    """The ApSrc of a (virtual) fp32 feature; reading mean / rstd finalises pending statistics.
+    bf16_bit: ap_src.act bit 8 tells the kernel that ``data`` holds bf16 values (where the C side can read those)."""
+    s = C.ApSrc()
+    s.data, s.C = f.data.data_ptr(), f.data.shape[1]
+    s.act = f.act | (0x100 if bf16_bit and f.data.dtype == torch.bfloat16 else 0)
+    if f.virtual:
+        s.mean, s.rstd = f.mean.data_ptr(), f.rstd.data_ptr()
+    return s
+
+
 def presplit(f, precision=None):
     """Split-bf16 copy of a (virtual) feature: XS[n][head|tail][C/8][H*W][8 x bf16] with the producer's
     InstanceNorm + activation applied (ap_split_prepass).  Cached on the Feat: one pass serves every consumer.
@@ -413,12 +437,8 @@ def presplit_rows(f, k, pad, pad_mode):
         x = f.data
         n, c, h, w = x.shape
         _require_device(x, 'stem input')
-        s = C.ApSrc()
-        s.data, s.C, s.act = x.data_ptr(), c, f.act
-        if f.virtual:
-            s.mean, s.rstd = f.mean.data_ptr(), f.rstd.data_ptr()
-        nbytes = C.check(C.lib().ap_split_prepass_bytes(n, ROW_CHANNELS, h, w), 'split_prepass_bytes')
-        xs = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        s = _src_of(f)
+        xs = _alloc_xs((n, ROW_CHANNELS, h, w), x.device)
         C.check(C.lib().ap_split_prepass_rows(ctypes.byref(s), n, h, w, k, pad, pad_mode, _ptr(xs), _stream()),
                 'split_prepass_rows')
         hit = Feat.split_only((n, ROW_CHANNELS, h, w), xs)
@@ -460,21 +480,17 @@ def presplit_s2d(f):
     x = f.data
     n, c, h, w = x.shape
     _require_device(x, 'space-to-depth source')
-    s = C.ApSrc()
-    s.data, s.C, s.act = x.data_ptr(), c, f.act
-    if f.virtual:
-        s.mean, s.rstd = f.mean.data_ptr(), f.rstd.data_ptr()
+    s = _src_of(f)
     shape = (n, 4 * c, h // 2 + 1, w // 2 + 1)
-    nbytes = C.check(C.lib().ap_split_prepass_bytes(*shape), 'split_prepass_bytes')
-    xs = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    xs = _alloc_xs(shape, x.device)
     C.check(C.lib().ap_split_prepass_s2d(ctypes.byref(s), n, h, w, _ptr(xs), _stream()), 'split_prepass_s2d')
     return Feat.split_only(shape, xs)
 
 
-def _alloc_xs(x):
-    n, c, h, w = x.shape
-    nbytes = C.check(C.lib().ap_split_prepass_bytes(n, c, h, w), 'split_prepass_bytes')
-    return torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+def _alloc_xs(shape, device):
+    """The buffer of the split-bf16 copy of a feature of ``shape``."""
+    nbytes = C.check(C.lib().ap_split_prepass_bytes(*shape), 'split_prepass_bytes')
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
 def _norm_apply_split(f, residual, want_y, want_xs, xs_relu=False):
@@ -490,7 +506,7 @@ def _norm_apply_split(f, residual, want_y, want_xs, xs_relu=False):
         _require_device(f.oct, 'norm/split source')
     else:
         _require_device(x, 'norm/split source', allow_bf16=True)
-    s = C.ApSrc()
+    s = C.ApSrc()          # by hand, not _src_of: pending statistics are finalised INSIDE this pass, so _mean / pending are read raw
     s.data, s.C, s.act = (f.oct if oct_src else x).data_ptr(), c, f.act
     partial, tiles, mo, ro = None, 0, None, None
     if f.pending is not None:
@@ -519,7 +535,7 @@ def _norm_apply_split(f, residual, want_y, want_xs, xs_relu=False):
             if residual.virtual:
                 r.mean, r.rstd = residual.mean.data_ptr(), residual.rstd.data_ptr()
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device) if want_y else None
-    xs = _alloc_xs(x) if want_xs else None
+    xs = _alloc_xs(x.shape, x.device) if want_xs else None
     # plain-bf16 mode: no kernel reads tail planes, so they are not written (the package-wide mode decides: split
     # copies are shared by every consumer of a feature)
     flags = ((1 if DEFAULT_PRECISION == PRECISION_BF16 else 0) | (2 if xs_relu else 0) | res_flag |
@@ -583,14 +599,10 @@ def conv2d(spec, srcs, packed, bias=None, act=ACT_NONE, want_stats=False, out_ac
     if spec.precision != PRECISION_FP32 and C.check(lib.ap_conv2d_wants_presplit(ctypes.byref(d)), 'wants_presplit'):
         # this layer runs on the split-bf16 matrix path: hand it the split copies of its sources (made, together
         # with the sources' pending InstanceNorm statistics, in one pass each)
-        d.presplit = 1
         if spec.precision == PRECISION_BF16X3 and DEFAULT_PRECISION == PRECISION_BF16:
             raise RuntimeError('a split-bf16 (bf16x3) layer cannot run while the package mode is plain bf16: split copies '
                                'are then written without their tail planes')
-        for i, f in enumerate(srcs):
-            d.src[i].data = presplit(f, spec.precision).data_ptr()
-            d.src[i].mean = d.src[i].rstd = None
-            d.src[i].act = ACT_NONE
+        spec.presplit_desc(n, h, w, srcs, d=d)
     else:
         if any(f.is_split_only for f in srcs):
             raise RuntimeError('conv2d: a source exists only as its split-bf16 copy but this layer reads fp32')
@@ -623,7 +635,7 @@ def conv2d(spec, srcs, packed, bias=None, act=ACT_NONE, want_stats=False, out_ac
         macs = getattr(spec, 'alg_macs', None) or sum(spec.cin_segments) * spec.k ** 2
         PROFILER.records.append((buf.value.decode(), 2.0 * n * px * spec.cout * macs, e0, e1))
     if out_octet:
-        res = Feat(torch.empty(1, dtype=torch.float32, device=x0.device).expand((n, spec.cout, ho.value, wo.value)),
+        res = Feat(_stand_in((n, spec.cout, ho.value, wo.value), x0.device),
                    act=out_act if want_stats else ACT_NONE, pending=(partial, tiles) if want_stats else None)
         res.oct = y
         return res
@@ -670,8 +682,7 @@ def fused_norm_ok(spec, srcs):
     if not FUSED_NORM or spec.precision != PRECISION_BF16X3 or DEFAULT_PRECISION != PRECISION_BF16X3:
         return False
     n, _, h, w = srcs[0].data.shape
-    d = spec.desc(n, h, w, None, ACT_NONE)
-    d.presplit = 1
+    d = spec.presplit_desc(n, h, w)
     return C.lib().ap_conv2d_fused_norm_ok(ctypes.byref(d)) == 1
 
 
@@ -682,12 +693,7 @@ def conv2d_norm(spec, srcs, packed, act=ACT_NONE, residual=None, want_oct=False,
     want_oct: what the next block's residual add reads); its NCHW tensor is never written."""
     x0 = srcs[0].data
     n, _, h, w = x0.shape
-    d = spec.desc(n, h, w, None, ACT_NONE)
-    d.presplit = 1
-    for i, f in enumerate(srcs):
-        d.src[i].data = presplit(f, spec.precision).data_ptr()
-        d.src[i].mean = d.src[i].rstd = None
-        d.src[i].act = ACT_NONE
+    d = spec.presplit_desc(n, h, w, srcs)
     lib = C.lib()
     ho, wo = ctypes.c_int32(), ctypes.c_int32()
     C.check(lib.ap_conv2d_out_size(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), 'conv2d_out_size')
@@ -716,8 +722,7 @@ def conv2d_norm(spec, srcs, packed, act=ACT_NONE, residual=None, want_oct=False,
         y_oct = torch.empty((n, cout // 8, hw, 8), dtype=torch.float32, device=dev)
         fn.y_oct = y_oct.data_ptr()
     if want_xs:
-        nbytes = C.check(lib.ap_split_prepass_bytes(n, cout, ho.value, wo.value), 'split_prepass_bytes')
-        xs = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        xs = _alloc_xs((n, cout, ho.value, wo.value), dev)
         fn.xs = xs.data_ptr()
     if PROFILER is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -730,7 +735,7 @@ def conv2d_norm(spec, srcs, packed, act=ACT_NONE, residual=None, want_oct=False,
     _FNORM_FLAGS.append(counters)
     if len(_FNORM_FLAGS) > 256:
         check_fused_norm()
-    res = Feat(torch.empty(1, dtype=torch.float32, device=dev).expand((n, cout, ho.value, wo.value)))
+    res = Feat(_stand_in((n, cout, ho.value, wo.value), dev))
     res.xs, res.oct = xs, y_oct
     return res
 
@@ -750,12 +755,7 @@ def _conv2d_view(spec, srcs, packed, out, view):
     activation, no statistics)."""
     x0 = srcs[0].data
     n, _, h, w = x0.shape
-    d = spec.desc(n, h, w, None, ACT_NONE)
-    d.presplit = 1
-    for i, f in enumerate(srcs):
-        d.src[i].data = presplit(f, spec.precision).data_ptr()
-        d.src[i].mean = d.src[i].rstd = None
-        d.src[i].act = ACT_NONE
+    d = spec.presplit_desc(n, h, w, srcs)
     fn = C.lib().ap_conv2d_fwd_view_bf16out if out.dtype == torch.bfloat16 else C.lib().ap_conv2d_fwd_view
     C.check(fn(ctypes.byref(d), ctypes.byref(view), _ptr(packed), None, _ptr(out), _stream()), 'conv2d_fwd_view')
 
@@ -784,22 +784,15 @@ def conv2d_dgrad_strip(spec, g, packed, packed_t, strip=None, out_bf16=False):
     n, c, h, w = g.data.shape
     hp, wp = h + 2, w + 2
     # out_bf16: the gradient is stored as bf16 (plain-bf16 train step; its only reader is ap_instnorm_bwd_split, which is told)
-    d0 = spec.desc(n, h, w, None, ACT_NONE)
-    d0.presplit = 1
-    out_bf16 = bool(out_bf16) and C.lib().ap_conv2d_bf16out_ok(ctypes.byref(d0)) == 1
+    out_bf16 = bool(out_bf16) and C.lib().ap_conv2d_bf16out_ok(ctypes.byref(spec.presplit_desc(n, h, w))) == 1
     out = torch.empty((n, spec.cout, hp, wp), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=g.data.device)
     if strip is None and g.is_split_only:
         raise RuntimeError('conv2d_dgrad_strip: the gradient exists only as its split copy and no column strip was prepared '
                            '(ap_instnorm_bwd_split writes it when the backward plan asks for one)')
     t = strip if strip is not None else Feat(g.data[:, :, :, w - 2:].transpose(2, 3).contiguous())   # strip: (N, C, 2, H) from instnorm_bwd_split
-    v = C.ApOutView()
-    v.nstride, v.cstride = spec.cout * hp * wp, hp * wp
-    v.rstride, v.xstride, v.y_off, v.x_off, v.OH, v.OW = 1, wp, w - 2, 0, 4, hp
-    _conv2d_view(spec, [t], packed_t, out, v)
-    v2 = C.ApOutView()
-    v2.nstride, v2.cstride = spec.cout * hp * wp, hp * wp
-    v2.rstride, v2.xstride, v2.y_off, v2.x_off, v2.OH, v2.OW = wp, 1, 0, 0, hp, w
-    _conv2d_view(spec, [g], packed, out, v2)
+    # ApOutView: nstride, cstride, rstride, xstride, y_off, x_off, OH, OW
+    _conv2d_view(spec, [t], packed_t, out, C.ApOutView(spec.cout * hp * wp, hp * wp, 1, wp, w - 2, 0, 4, hp))
+    _conv2d_view(spec, [g], packed, out, C.ApOutView(spec.cout * hp * wp, hp * wp, wp, 1, 0, 0, hp, w))
     return out
 
 
@@ -863,14 +856,13 @@ def warp_concat(f, motion, flow, ifmask, level, emit_xs=False, keep_fp32=True, s
         out = torch.empty((n, 2 * c, h, w), dtype=torch.float32, device=x.device)
     s2d_shape = (n, 8 * c, h // 2 + 1, w // 2 + 1)
     if emit_xs:
-        nbytes = C.check(C.lib().ap_split_prepass_bytes(*(s2d_shape if s2d else (n, 2 * c, h, w))), 'split_prepass_bytes')
-        xs = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        xs = _alloc_xs(s2d_shape if s2d else (n, 2 * c, h, w), x.device)
     C.check(C.lib().ap_warp_concat_fwd_ex(_ptr(x), _ptr(f.mean), _ptr(f.rstd), f.act, _ptr(motion), _ptr(flow),
                                           _ptr(ifmask), _ptr(out), _ptr(xs), n, c, h, w, s, 1.0 / (1 << level),
                                           (1 if s2d else 0) | (2 if f.oct is not None else 0), _stream()), 'warp_concat_fwd')
     if s2d:
         # the plain split copy does not exist: only the stride-2 consumer (through .s2d) or fp32 readers can use this
-        res = Feat(out) if out is not None else Feat(torch.empty(1, dtype=torch.float32, device=x.device).expand((n, 2 * c, h, w)))
+        res = Feat(out if out is not None else _stand_in((n, 2 * c, h, w), x.device))
         res.s2d = Feat.split_only(s2d_shape, xs)
         return res
     if out is None:
@@ -942,10 +934,7 @@ def wgrad(k, stride, pad, pad_mode, g, srcs, out_shape, precision=None, out=None
         f = srcs[0]
         _require_device(f.data, 'wgrad source')
         _require_device(g.data, 'wgrad gradient')
-        s = C.ApSrc()
-        s.data, s.C, s.act = f.data.data_ptr(), cin, f.act
-        if f.virtual:
-            s.mean, s.rstd = f.mean.data_ptr(), f.rstd.data_ptr()
+        s = _src_of(f)
         dw = _grad_out(out, out_shape, g.data.device)
         C.check(C.lib().ap_conv_head_wgrad(ctypes.byref(s), _ptr(g.data), n, f.data.shape[2], f.data.shape[3], k, pad,
                                            _ptr(dw), _stream()), 'conv_head_wgrad')
@@ -965,12 +954,8 @@ def wgrad(k, stride, pad, pad_mode, g, srcs, out_shape, precision=None, out=None
         if ok:
             _require_device(f.data, 'wgrad source')
             _require_device(g.data, 'wgrad gradient', allow_bf16=not final_form)
-            sw, sn = C.ApSrc(), C.ApSrc()
-            # ap_src.act bit 8: the stems' gradient as instnorm_bwd(out_bf16=True) stored it
-            sw.data, sw.C, sw.act = wide.data.data_ptr(), wide.data.shape[1], wide.act | (0x100 if wide.data.dtype == torch.bfloat16 else 0)
-            if wide.virtual:
-                sw.mean, sw.rstd = wide.mean.data_ptr(), wide.rstd.data_ptr()
-            sn.data, sn.C, sn.act = narrow.data.data_ptr(), narrow.data.shape[1], ACT_NONE
+            sw = _src_of(wide, bf16_bit=True)       # (bf16: the stems' gradient as instnorm_bwd(out_bf16=True) stored it)
+            sn = C.ApSrc(narrow.data.data_ptr(), None, None, narrow.data.shape[1], ACT_NONE)
             ws = torch.empty(C.check(C.lib().ap_wgrad_k7_bf16_workspace_floats(n, sw.C, sn.C, h, w, final_form), 'wgrad_k7_ws'),
                              dtype=torch.float32, device=g.data.device)
             dw = _grad_out(out, out_shape, g.data.device)
@@ -1003,10 +988,7 @@ def wgrad(k, stride, pad, pad_mode, g, srcs, out_shape, precision=None, out=None
         f = srcs[0]
         _require_device(f.data, 'wgrad source')
         _require_device(g.data, 'wgrad gradient')
-        s = C.ApSrc()
-        s.data, s.C, s.act = f.data.data_ptr(), cin, f.act
-        if f.virtual:
-            s.mean, s.rstd = f.mean.data_ptr(), f.rstd.data_ptr()
+        s = _src_of(f)
         h, w = f.data.shape[2:]
         ws = torch.empty(C.check(C.lib().ap_conv_final_wgrad_workspace_floats(n, cin, h, w), 'conv_final_wgrad_ws'),
                          dtype=torch.float32, device=g.data.device)
@@ -1050,17 +1032,10 @@ def _wgrad_desc(k, stride, pad, pad_mode, g_shape, g, srcs, precision):
     d.g.C, d.g.act = m, ACT_NONE
     if g is not None:
         _require_device(g.data, 'wgrad gradient')
-        d.g.data = g.data.data_ptr()
-        d.g.mean = g.mean.data_ptr() if g.mean is not None else None
-        d.g.rstd = g.rstd.data_ptr() if g.rstd is not None else None
-        d.g.act = g.act
+        d.g = _src_of(g)
     for i, f in enumerate(srcs):
         _require_device(f.data, 'wgrad source', allow_bf16=True)
-        d.src[i].data = f.data.data_ptr()
-        d.src[i].mean = f.mean.data_ptr() if f.mean is not None else None
-        d.src[i].rstd = f.rstd.data_ptr() if f.rstd is not None else None
-        # ap_src.act bit 8: the segment holds bf16 values (the C side refuses it where its kernels cannot read them)
-        d.src[i].C, d.src[i].act = f.data.shape[1], f.act | (0x100 if f.data.dtype == torch.bfloat16 else 0)
+        d.src[i] = _src_of(f, bf16_bit=True)       # (the C side refuses bf16 values where its kernels cannot read them)
     # the split copies the forward pass staged of the same sources (still alive on the tape): the C side re-tiles the shifted
     # operand from them instead of normalising + splitting the fp32 tensors again (ap_wgrad_desc.src_xs)
     if XS_WGRAD:
@@ -1117,10 +1092,7 @@ def pad_materialize(srcs, pad, pad_mode, hp=None, wp=None):
     arr = (C.ApSrc * len(srcs))()
     for i, f in enumerate(srcs):
         _require_device(f.data, 'pad_materialize source')
-        arr[i].data = f.data.data_ptr()
-        arr[i].mean = f.mean.data_ptr() if f.mean is not None else None
-        arr[i].rstd = f.rstd.data_ptr() if f.rstd is not None else None
-        arr[i].C, arr[i].act = f.data.shape[1], f.act
+        arr[i] = _src_of(f)
     out = torch.empty((n, sum(f.data.shape[1] for f in srcs), hp, wp), dtype=torch.float32, device=x0.device)
     C.check(C.lib().ap_pad_materialize(arr, len(srcs), n, h, w, pad, pad_mode, hp, wp, _ptr(out), _stream()),
             'pad_materialize')
@@ -1290,7 +1262,7 @@ def instnorm_bwd_split(red, f, gt_dims=None, want_xs=True, want_strip=False, wan
     n, c, h, w = f.data.shape
     dev = f.data.device
     heads_only = DEFAULT_PRECISION == PRECISION_BF16
-    xs = _alloc_xs(f.data) if want_xs else None
+    xs = _alloc_xs(f.data.shape, dev) if want_xs else None
     gt = dims = None
     if gt_dims is not None:
         ghp, gx8, mp = gt_dims
