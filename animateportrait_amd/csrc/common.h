@@ -1,8 +1,12 @@
-// common.h -- error reporting shared by the C-ABI translation units.
+// common.h -- error reporting and host helpers shared by the C-ABI translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <mutex>
+#include <vector>
 #include "../../include/animateportrait_amd.h"
 
 // Ablation switches (skip the DMA refill / the barriers / the epilogue of the matrix kernels, APAMD_ABLATE=<bits>)
@@ -28,6 +32,51 @@ template <class Seg>
 inline void fill_seg(Seg& seg, const ap_src& s, int chunk_begin, bool with_norm = true) {
     seg.data = s.data; seg.C = s.C; seg.chunk_begin = chunk_begin;
     if (with_norm) { seg.mean = s.mean; seg.rstd = s.rstd; seg.act = s.act; }
+}
+// A/B switches are integers on both sides of the boundary: APAMD_X=0 means "off", as ops.py reads it
+inline int env_int(const char* name, int dflt) {
+    const char* s = getenv(name);
+    return s ? atoi(s) : dflt;
+}
+// compute units of the current device (cached per device ordinal); without a device: the MI355X's 256
+inline int num_cus() {
+    static std::mutex mu;
+    static int cached[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!cached[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
+        cached[dev] = n;
+    }
+    return cached[dev];
+}
+// raises a kernel's dynamic-LDS limit to `bytes`, once per process and kernel
+inline int ensure_dyn_lds(const void* fn, int bytes) {
+    static std::mutex mu;
+    static std::vector<const void*> done;
+    std::lock_guard<std::mutex> lk(mu);
+    for (const void* f : done)
+        if (f == fn) return AP_OK;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    done.push_back(fn);
+    return AP_OK;
+}
+inline long long round4(long long x) { return (x + 3) / 4 * 4; }
+// R rows of each of N images dealt to about one workgroup per CU (its LDS fills one): bpi workgroups of RB rows per image.
+// even: RB is even (a workgroup takes its rows in pairs) and no workgroup gets fewer than two rows
+struct RowSplit {
+    int bpi, RB, grid;
+};
+inline RowSplit split_rows(int N, int R, bool even) {
+    int bpi = std::max(1, (num_cus() + N - 1) / N);
+    if (even && bpi > R / 2) bpi = std::max(1, R / 2);
+    int RB = (R + bpi - 1) / bpi;
+    if (even) RB += RB & 1;
+    bpi = (R + RB - 1) / RB;
+    return RowSplit{bpi, RB, N * bpi};
 }
 // InstanceNorm statistics: planes with mean^2 > ratio * var (as estimated from the conv epilogue's fp32 sums) are
 // recomputed from the data (instnorm.hip: instnorm_finalize_kernel, conv_bf16x3.h: norm_split_kernel)

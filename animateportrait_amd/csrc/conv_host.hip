@@ -14,7 +14,6 @@
 
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 namespace apamd {
@@ -107,13 +106,6 @@ struct Plan {
     int Hout = 0, Wout = 0, stat_tiles = 0;
     long long packed_floats = 0;
 };
-
-static int env_int(const char* name, int dflt) {
-    const char* s = getenv(name);
-    return s ? atoi(s) : dflt;
-}
-
-static int num_cus();
 
 // ------------------------------------------------------------------ make_plan, in steps
 struct Geom {
@@ -492,34 +484,6 @@ static const void* direct_fn(int K, int cop) {
 static size_t direct_lds_bytes(int K, int cop, int nbuf, int cin_pad) {
     if (cop == 1) return 4 * DirectCfg<7, 1>::lds_floats(nbuf, cin_pad);
     return 4 * DirectCfg<7, 4>::lds_floats(nbuf, cin_pad);
-}
-
-static std::mutex g_attr_mu;
-static std::vector<const void*> g_attr_done;
-
-static int ensure_lds_attr(const void* fn) {
-    std::lock_guard<std::mutex> lk(g_attr_mu);
-    for (auto f : g_attr_done)
-        if (f == fn) return AP_OK;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    g_attr_done.push_back(fn);
-    return AP_OK;
-}
-
-// compute units of the current device (cached per device ordinal)
-static int num_cus() {
-    static std::mutex mu;
-    static int cached[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!cached[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-        cached[dev] = n;
-    }
-    return cached[dev];
 }
 
 // the packer's parameters for one launch of a split-bf16 plan; `v` (nullable): the weight as a strided / derived view
@@ -961,7 +925,7 @@ static int launch_small(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a)
 
 static int launch_direct(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
     const void* kfn = direct_fn(d->KH, pl.direct_cop);
-    int rc = ensure_lds_attr(kfn);
+    int rc = ensure_dyn_lds(kfn, 160 * 1024);
     if (rc) return rc;
     DirectKParams p;
     memset(&p, 0, sizeof(p));
@@ -1012,7 +976,7 @@ static int tap_bits(const Launch& L, unsigned& bits) {
 }
 
 static int launch_igemm(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
-    int rc = ensure_lds_attr(pl.k->fn);
+    int rc = ensure_dyn_lds(pl.k->fn, 160 * 1024);
     if (rc) return rc;
     for (const auto& L : pl.launches) {
         ConvKParams p = conv_params(d, pl, L, a, true);
@@ -1132,7 +1096,7 @@ static int launch_bf3(const ap_conv_desc* d, const Plan& pl, const OutForm& o, c
             p.fn_mean = fn->mean; p.fn_rstd = fn->rstd; p.fn_counters = fn->counters;
             p.fn_debug = env_int("APAMD_FNORM_DEBUG", 0);
         }
-        rc = ensure_lds_attr(kfn);
+        rc = ensure_dyn_lds(kfn, 160 * 1024);
         if (rc) return rc;
         size_t lds = kern->lds(d->precision, p.ntaps);
         bool sb = false;
@@ -1142,7 +1106,7 @@ static int launch_bf3(const ap_conv_desc* d, const Plan& pl, const OutForm& o, c
             // rejected experiment kept for A/B (tools/variants/conv_bf16x3_sb.h, `make variants`): one LDS stage per
             // workgroup, two workgroups per CU
             kfn = bf3_sb_kernel(&lds);
-            rc = ensure_lds_attr(kfn);
+            rc = ensure_dyn_lds(kfn, 160 * 1024);
             if (rc) return rc;
             p.fn_debug = env_int("APAMD_CONV_SB_SKEW", 0);
             sb = true;

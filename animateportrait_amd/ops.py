@@ -917,6 +917,13 @@ def _grad_out(out, shape, device):
     return out
 
 
+def _wgrad_buffers(nfloats, what, out, out_shape, device):
+    """What a weight-gradient route launches into: the workspace its ``*_workspace_floats`` query asked for (a refusal raises)
+    and the tensor the gradient goes to (``out``, the layer's slot, or a new one)."""
+    ws = torch.empty(C.check(nfloats, what), dtype=torch.float32, device=device)
+    return ws, _grad_out(out, out_shape, device)
+
+
 def wgrad(k, stride, pad, pad_mode, g, srcs, out_shape, precision=None, out=None, g_t=None, g_xs=None):
     """Weight gradient (see include/animateportrait_amd.h: ap_conv2d_wgrad).  g: Feat of the M-role tensor,
     srcs: Feats of the shifted tensor's segments.  Returns a tensor of ``out_shape`` (OIHW / IOHW): ``out`` when given
@@ -924,86 +931,110 @@ def wgrad(k, stride, pad, pad_mode, g, srcs, out_shape, precision=None, out=None
     precision: PRECISION_* (default: the package default, i.e. split-bf16 for the wide stride-1 layers).
     g_t: the M-role operand as instnorm_bwd_split wrote it (wgrad_gt_dims); ``g`` then only carries the shape.
     g_xs: the split copy of the gradient (instnorm_bwd_split's ``xs``): where the layer is served by ap_conv2d_wgrad_xs (both operands
-    read as the convolutions' split copies, no preparation) that route is taken; ``g`` again only carries the shape."""
-    n, m, gh, gw = g.data.shape
+    read as the convolutions' split copies, no preparation) that route is taken; ``g`` again only carries the shape.
+    The edge layers have kernels of their own; they are tried first, in this order."""
+    m = g.data.shape[1]
     cin = sum(f.data.shape[1] for f in srcs)
-    if (m == 1 and k == 4 and stride == 1 and len(srcs) == 1 and cin >= 64 and not g.virtual and g.act == ACT_NONE and
-            tuple(out_shape) == (1, cin, k, k) and srcs[0].data.shape[2] <= 32 and srcs[0].data.shape[3] <= 31 and
-            pad == 1 and pad_mode == PAD_ZERO):
-        # PatchGAN output layer: one workgroup per input channel (conv_head.h)
-        f = srcs[0]
-        _require_device(f.data, 'wgrad source')
-        _require_device(g.data, 'wgrad gradient')
-        s = _src_of(f)
-        dw = _grad_out(out, out_shape, g.data.device)
-        C.check(C.lib().ap_conv_head_wgrad(ctypes.byref(s), _ptr(g.data), n, f.data.shape[2], f.data.shape[3], k, pad,
-                                           _ptr(dw), _stream()), 'conv_head_wgrad')
-        return dw
     prec = DEFAULT_PRECISION if precision is None else precision
-    if (K7_WGRAD and prec == PRECISION_BF16 and k == 7 and stride == 1 and pad == 3 and pad_mode == PAD_REFLECT and len(srcs) == 1 and
-            g_t is None and g_xs is None and not g.virtual and g.act == ACT_NONE and srcs[0].data.dtype == torch.float32):
-        # the 7x7 edge layers at full resolution, plain-bf16 arithmetic: one pass over the wide tensor on the bf16 matrix pipe
-        # (wgrad_k7.h) -- the stems (wide = the gradient) and the last layer (wide = the input)
-        f = srcs[0]
-        h, w = f.data.shape[2:]
-        final_form = 1 if (m == 1 and cin >= 32) else 0
-        wide, narrow = (f, g) if final_form else (g, f)
-        ok = ((final_form or not f.virtual and f.act == ACT_NONE) and tuple(out_shape) == (m, cin, k, k) and
-              (g.data.dtype == torch.float32 or not final_form) and
-              C.lib().ap_wgrad_k7_bf16_ok(n, wide.data.shape[1], narrow.data.shape[1], h, w, final_form) == 1)
-        if ok:
-            _require_device(f.data, 'wgrad source')
-            _require_device(g.data, 'wgrad gradient', allow_bf16=not final_form)
-            sw = _src_of(wide, bf16_bit=True)       # (bf16: the stems' gradient as instnorm_bwd(out_bf16=True) stored it)
-            sn = C.ApSrc(narrow.data.data_ptr(), None, None, narrow.data.shape[1], ACT_NONE)
-            ws = torch.empty(C.check(C.lib().ap_wgrad_k7_bf16_workspace_floats(n, sw.C, sn.C, h, w, final_form), 'wgrad_k7_ws'),
-                             dtype=torch.float32, device=g.data.device)
-            dw = _grad_out(out, out_shape, g.data.device)
-            if PROFILER is not None:
-                PROFILER.note('wgrad_k7<%s>' % ('final' if final_form else 'stem'))
-            C.check(C.lib().ap_wgrad_k7_bf16(ctypes.byref(sw), ctypes.byref(sn), n, h, w, final_form, _ptr(ws), _ptr(dw), _stream()),
-                    'wgrad_k7_bf16')
+    one_src, own_g, plain_g = len(srcs) == 1, g_t is None and g_xs is None, not g.virtual and g.act == ACT_NONE
+    oihw = tuple(out_shape) == (m, cin, k, k)
+    if (m == 1 and k == 4 and stride == 1 and one_src and cin >= 64 and plain_g and oihw and srcs[0].data.shape[2] <= 32 and
+            srcs[0].data.shape[3] <= 31 and pad == 1 and pad_mode == PAD_ZERO):
+        return _wgrad_head(k, pad, g, srcs[0], out_shape, out)
+    if (K7_WGRAD and prec == PRECISION_BF16 and k == 7 and stride == 1 and pad == 3 and pad_mode == PAD_REFLECT and one_src and
+            own_g and plain_g and srcs[0].data.dtype == torch.float32):
+        dw = _wgrad_k7(k, g, srcs[0], out_shape, out)
+        if dw is not None:
             return dw
-    if g.data.dtype == torch.bfloat16 and g_t is None and g_xs is None:
+    if g.data.dtype == torch.bfloat16 and own_g:
         g = Feat(g.data.float(), g._mean, g._rstd, g.act)       # (only wgrad_k7 reads a bf16-stored gradient)
-    if (D0_MFMA and prec == PRECISION_BF16 and k == 4 and stride == 2 and pad == 1 and pad_mode == PAD_ZERO and len(srcs) == 1 and
-            g_t is None and g_xs is None and not g.virtual and g.act == ACT_NONE and not srcs[0].virtual and srcs[0].act == ACT_NONE and
-            not srcs[0].is_split_only and srcs[0].data.dtype == torch.float32 and tuple(out_shape) == (m, cin, k, k)):
-        # the PatchGAN's first layer, plain-bf16 arithmetic: one pass over the gradient on the bf16 matrix pipe (wgrad_k7.h, form 2)
-        f = srcs[0]
-        h, w = f.data.shape[2:]
-        if (gh, gw) == (h // 2, w // 2) and C.lib().ap_wgrad_d0_bf16_ok(n, m, cin, h, w) == 1:
-            _require_device(f.data, 'wgrad source')
-            _require_device(g.data, 'wgrad gradient')
-            ws = torch.empty(C.check(C.lib().ap_wgrad_d0_bf16_workspace_floats(n, m, cin, h, w), 'wgrad_d0_ws'),
-                             dtype=torch.float32, device=g.data.device)
-            dw = _grad_out(out, out_shape, g.data.device)
-            if PROFILER is not None:
-                PROFILER.note('wgrad_k7<d0>')
-            C.check(C.lib().ap_wgrad_d0_bf16(_ptr(g.data), _ptr(f.data), n, m, cin, h, w, _ptr(ws), _ptr(dw), _stream()), 'wgrad_d0_bf16')
+    if (D0_MFMA and prec == PRECISION_BF16 and k == 4 and stride == 2 and pad == 1 and pad_mode == PAD_ZERO and one_src and
+            own_g and plain_g and not srcs[0].virtual and srcs[0].act == ACT_NONE and not srcs[0].is_split_only and
+            srcs[0].data.dtype == torch.float32 and oihw):
+        dw = _wgrad_d0(g, srcs[0], out_shape, out)
+        if dw is not None:
             return dw
-    if (m == 1 and k == 7 and stride == 1 and pad == 3 and len(srcs) == 1 and cin >= 16 and not g.virtual and
-            g.act == ACT_NONE and tuple(out_shape) == (1, cin, k, k)):
-        # the generator's last layer: vector-ALU kernel, window through LDS (wgrad_final.h)
-        f = srcs[0]
-        _require_device(f.data, 'wgrad source')
-        _require_device(g.data, 'wgrad gradient')
-        s = _src_of(f)
-        h, w = f.data.shape[2:]
-        ws = torch.empty(C.check(C.lib().ap_conv_final_wgrad_workspace_floats(n, cin, h, w), 'conv_final_wgrad_ws'),
-                         dtype=torch.float32, device=g.data.device)
-        dw = _grad_out(out, out_shape, g.data.device)
-        C.check(C.lib().ap_conv_final_wgrad(ctypes.byref(s), _ptr(g.data), n, h, w, k, pad, pad_mode, _ptr(ws), _ptr(dw),
-                                            _stream()), 'conv_final_wgrad')
-        return dw
-    if m <= 4 and stride == 1 and cin >= 16 and tuple(out_shape) == (m, cin, k, k) and 2 * pad == k - 1:
+    if m == 1 and k == 7 and stride == 1 and pad == 3 and one_src and cin >= 16 and plain_g and oihw:
+        return _wgrad_final(k, pad, pad_mode, g, srcs[0], out_shape, out)
+    if m <= 4 and stride == 1 and cin >= 16 and oihw and 2 * pad == k - 1:
         dw = _wgrad_few_outputs(k, pad, pad_mode, g, srcs, out_shape)
         return dw if out is None else out.copy_(dw)
+    return _wgrad_general(k, stride, pad, pad_mode, g, srcs, out_shape, precision, out, g_t, g_xs)
+
+
+def _wgrad_head(k, pad, g, f, out_shape, out):
+    """PatchGAN output layer: one workgroup per input channel (conv_head.h)"""
+    _require_device(f.data, 'wgrad source')
+    _require_device(g.data, 'wgrad gradient')
+    s = _src_of(f)
+    dw = _grad_out(out, out_shape, g.data.device)
+    C.check(C.lib().ap_conv_head_wgrad(ctypes.byref(s), _ptr(g.data), g.data.shape[0], f.data.shape[2], f.data.shape[3], k, pad,
+                                       _ptr(dw), _stream()), 'conv_head_wgrad')
+    return dw
+
+
+def _wgrad_k7(k, g, f, out_shape, out):
+    """The 7x7 edge layers at full resolution, plain-bf16 arithmetic: one pass over the wide tensor on the bf16 matrix pipe
+    (wgrad_k7.h) -- the stems (wide = the gradient) and the last layer (wide = the input).  None: the shape is not served."""
+    n, m = g.data.shape[:2]
+    cin, h, w = f.data.shape[1:]
+    final_form = 1 if (m == 1 and cin >= 32) else 0
+    wide, narrow = (f, g) if final_form else (g, f)
+    if not ((final_form or not f.virtual and f.act == ACT_NONE) and tuple(out_shape) == (m, cin, k, k) and
+            (g.data.dtype == torch.float32 or not final_form) and
+            C.lib().ap_wgrad_k7_bf16_ok(n, wide.data.shape[1], narrow.data.shape[1], h, w, final_form) == 1):
+        return None
+    _require_device(f.data, 'wgrad source')
+    _require_device(g.data, 'wgrad gradient', allow_bf16=not final_form)
+    sw = _src_of(wide, bf16_bit=True)       # (bf16: the stems' gradient as instnorm_bwd(out_bf16=True) stored it)
+    sn = C.ApSrc(narrow.data.data_ptr(), None, None, narrow.data.shape[1], ACT_NONE)
+    ws, dw = _wgrad_buffers(C.lib().ap_wgrad_k7_bf16_workspace_floats(n, sw.C, sn.C, h, w, final_form), 'wgrad_k7_ws', out, out_shape,
+                            g.data.device)
+    if PROFILER is not None:
+        PROFILER.note('wgrad_k7<%s>' % ('final' if final_form else 'stem'))
+    C.check(C.lib().ap_wgrad_k7_bf16(ctypes.byref(sw), ctypes.byref(sn), n, h, w, final_form, _ptr(ws), _ptr(dw), _stream()),
+            'wgrad_k7_bf16')
+    return dw
+
+
+def _wgrad_d0(g, f, out_shape, out):
+    """The PatchGAN's first layer, plain-bf16 arithmetic: one pass over the gradient on the bf16 matrix pipe (wgrad_k7.h, form 2).
+    None: the shape is not served."""
+    n, m, gh, gw = g.data.shape
+    cin, h, w = f.data.shape[1:]
+    if (gh, gw) != (h // 2, w // 2) or C.lib().ap_wgrad_d0_bf16_ok(n, m, cin, h, w) != 1:
+        return None
+    _require_device(f.data, 'wgrad source')
+    _require_device(g.data, 'wgrad gradient')
+    ws, dw = _wgrad_buffers(C.lib().ap_wgrad_d0_bf16_workspace_floats(n, m, cin, h, w), 'wgrad_d0_ws', out, out_shape, g.data.device)
+    if PROFILER is not None:
+        PROFILER.note('wgrad_k7<d0>')
+    C.check(C.lib().ap_wgrad_d0_bf16(_ptr(g.data), _ptr(f.data), n, m, cin, h, w, _ptr(ws), _ptr(dw), _stream()), 'wgrad_d0_bf16')
+    return dw
+
+
+def _wgrad_final(k, pad, pad_mode, g, f, out_shape, out):
+    """The generator's last layer: vector-ALU kernel, window through LDS (wgrad_final.h)"""
+    _require_device(f.data, 'wgrad source')
+    _require_device(g.data, 'wgrad gradient')
+    s = _src_of(f)
+    n = g.data.shape[0]
+    cin, h, w = f.data.shape[1:]
+    ws, dw = _wgrad_buffers(C.lib().ap_conv_final_wgrad_workspace_floats(n, cin, h, w), 'conv_final_wgrad_ws', out, out_shape,
+                            g.data.device)
+    C.check(C.lib().ap_conv_final_wgrad(ctypes.byref(s), _ptr(g.data), n, h, w, k, pad, pad_mode, _ptr(ws), _ptr(dw),
+                                        _stream()), 'conv_final_wgrad')
+    return dw
+
+
+def _wgrad_general(k, stride, pad, pad_mode, g, srcs, out_shape, precision, out, g_t, g_xs):
+    """ap_conv2d_wgrad and its forms with a prepared gradient: _xs (its split copy), _pre (the kernel's own layout)"""
+    n, m, gh, gw = g.data.shape
+    cin = sum(f.data.shape[1] for f in srcs)
     d = _wgrad_desc(k, stride, pad, pad_mode, (n, m, gh, gw), None if (g_t is not None or g_xs is not None) else g, srcs, precision)
     lib = C.lib()
-    nws = C.check(lib.ap_conv2d_wgrad_workspace_floats(ctypes.byref(d)), 'wgrad_workspace_floats')
-    ws = torch.empty(nws, dtype=torch.float32, device=srcs[0].data.device)
-    dw = _grad_out(out, out_shape, srcs[0].data.device)
+    ws, dw = _wgrad_buffers(lib.ap_conv2d_wgrad_workspace_floats(ctypes.byref(d)), 'wgrad_workspace_floats', out, out_shape,
+                            srcs[0].data.device)
     assert dw.numel() == m * cin * k * k
     if g_xs is not None:
         if lib.ap_conv2d_wgrad_xs_ok(ctypes.byref(d)) != 1:
