@@ -7,7 +7,7 @@ backward replays it in reverse, launching the data-gradient (the forward conv ke
 roles), weight-gradient, InstanceNorm/activation-backward and warp-backward kernels of libapamd.so.
 PyTorch only carries the resulting tensors to the optimiser / the collective.
 """
-import os
+import collections
 
 import torch
 
@@ -145,60 +145,93 @@ def _dgrad_spec_geometry(layer, seg_c):
     return ConvSpec([s.cout], seg_c, k, 2, s.pad, PAD_ZERO, True, 1 if k == 3 else 0, W_IOHW, False), 0
 
 
-def _split_backward_plan(tape, layer, srcs, out, contribs):
-    """Can the InstanceNorm backward of ``out`` write the operands of its consumers itself (ops.instnorm_bwd_split)?  Yes when every
-    consumer of the gradient is a bf16 matrix kernel: the weight gradient takes a prepared M-role operand (ops.wgrad_gt_dims) and
-    each data gradient stages split copies.  Returns (reduced contributions, gt_dims, want_xs, want_strip) or None."""
-    s = layer.spec
-    if s.transposed or s.precision == ops.PRECISION_FP32 or ops.DEFAULT_PRECISION == ops.PRECISION_FP32:
-        return None
-    n, c, h, w = out.data.shape
-    pads = sorted(p for _, p in contribs if p > 0)
-    if pads and pads[-1] > 1:
-        return None
-    # the decision depends on shapes and on who wants a gradient, not on values: kept per layer (a handful of C-side plan queries
-    # per layer and step otherwise)
-    key = (n, c, h, w, bool(pads), layer.weight.requires_grad, tuple(tape.tracked(f) for f in srcs),
-           tuple(tuple(f.data.shape) for f in srcs), s.precision, ops.DEFAULT_PRECISION,
-           tuple(os.environ.get(v) for v in ('APAMD_NO_INBWD_SPLIT', 'APAMD_NO_BF16X3', 'APAMD_NO_S2D')),
-           ops.XS_DIRECT, all(f.xs is not None for f in srcs))
-    cache = layer.__dict__.setdefault('_split_bwd_plans', {})
+# How one call of a layer's backward runs: decided once per form of the call (_backward_plan) and cached on the layer; the four
+# executors below only follow it.  A new backward route is a new value of one of these fields.
+#   norm_route     'split' (ops.instnorm_bwd_split writes its consumers' operands, no fp32 dy) | 'instnorm' | 'act_bias' | 'act'
+#   dy16           'instnorm' only: dy is stored as bf16 (its one reader is the stems' weight gradient on the bf16 matrix pipe)
+#   gt_dims, want_xs, want_strip   'split' only: the operands to write
+#   wgrad_route    ops.wgrad_route's answer; None: the weight is frozen
+#   wgrad_operand  'own' (the kernel reads dy) | 'g_t' | 'g_xs_from_split' | 'g_xs_presplit' (the split copy is made on the spot)
+#   dgrad          per source segment None (not tracked) or (route, fold_pad); route 'final_k7' | 'head' | 'strip' | 'conv'
+BackwardPlan = collections.namedtuple('BackwardPlan', 'norm_route dy16 gt_dims want_xs want_strip wgrad_route wgrad_operand dgrad')
+
+
+def _backward_plan(tape, layer, srcs, out, norm, act, contribs):
+    """The BackwardPlan of this call.  The decision depends on shapes, on which copies exist and on who wants a gradient, not on
+    values: that form, together with ops.backward_switches(), is the key it is kept under (a dozen C-side plan queries per layer
+    and step otherwise)."""
+    form = (norm, act, layer.spec.precision, layer.weight.requires_grad, layer.bias.requires_grad, ops.form_of(out),
+            tuple(sorted(p for _, p in contribs if p > 0)), tuple((ops.form_of(f), tape.tracked(f)) for f in srcs))
+    key = (form, ops.backward_switches())
+    cache = layer.__dict__.setdefault('_backward_plans', {})
     if key not in cache:
-        cache[key] = _split_backward_decision(tape, layer, srcs, out, bool(pads))
-    dec = cache[key]
-    if dec is None:
-        return None
-    return (ops._split_contribs(contribs),) + dec
+        cache[key] = _make_backward_plan(layer, *form)
+    return cache[key]
 
 
-def _split_backward_decision(tape, layer, srcs, out, folded):
+def _make_backward_plan(layer, norm, act, precision, w_grad, b_grad, out, pads, srcs):
+    """Reads forms (ops.form_of) and asks the C-side plan queries; touches no memory."""
     s = layer.spec
-    n, c, h, w = out.data.shape
-    if not ops.instnorm_bwd_split_ok(out, 1 if folded else 0):
+    forms = [f for f, _ in srcs]
+    g = ops.Form(out.shape, torch.float32, False, ACT_NONE, False, False, False, False)       # dy: a plain fp32 feature
+    dgrad = tuple(_dgrad_route(layer, c, g, f, len(srcs)) if tracked else None for c, (f, tracked) in zip(s.cin_segments, srcs))
+    geom = (s.k, s.stride, s.pad, s.pad_mode, out.shape, forms, precision)
+    # split-bf16 3x3 layers (and the PatchGAN's 4x4) whose sources carry their forward copies: the weight gradient reads the
+    # gradient's split copy itself (ap_conv2d_wgrad_xs) -- no prepared operand; plain bf16 keeps the prepared-operand kernel
+    xs_ok = (w_grad and not s.transposed and precision == ops.PRECISION_BF16X3 and ops.DEFAULT_PRECISION == ops.PRECISION_BF16X3 and
+             ops.wgrad_xs_ok(*geom))
+    split = _split_operands(layer, out, pads, w_grad, xs_ok, geom, dgrad) if norm else None
+    if split is not None:
+        norm_route, (gt_dims, want_xs) = 'split', split
+        operand = 'g_xs_from_split' if xs_ok else ('g_t' if gt_dims is not None else 'own')
+    else:
+        norm_route = 'instnorm' if norm else ('act_bias' if b_grad and act != ACT_NONE else 'act')
+        gt_dims, want_xs = None, False
+        # (the split copy the data-gradient convolution stages anyway, cached on the Feat, is the weight gradient's operand too)
+        operand = 'g_xs_presplit' if xs_ok and out.shape[1] % 8 == 0 else 'own'
+    route = None
+    if w_grad and s.transposed:         # dW[ci][co*k*k]: M-role = the layer input (virtual allowed), shifted tensor = dy (stride 2)
+        route = ops.wgrad_route(s.k, 2, s.pad, PAD_ZERO, forms[0], [g], layer.weight.shape, precision, False)
+    elif w_grad:
+        route = ops.wgrad_route(s.k, s.stride, s.pad, s.pad_mode, g, forms, layer.weight.shape, precision, operand != 'own')
+    # a stem (no data gradient: its input is an image) whose weight gradient runs on the bf16 matrix pipe: dy has one reader, which
+    # rounds it to bf16.  (The package mode is asked here, not by wgrad_route: ops.wgrad takes the route by the layer's precision)
+    dy16 = (norm_route == 'instnorm' and route == 'k7_stem' and not any(t for _, t in srcs) and
+            ops.DEFAULT_PRECISION == ops.PRECISION_BF16)
+    want_strip = norm_route == 'split' and any(d is not None and d[0] == 'strip' for d in dgrad)
+    return BackwardPlan(norm_route, dy16, gt_dims, want_xs, want_strip, route, operand, dgrad)
+
+
+def _dgrad_route(layer, seg_c, g, f, nsrc):
+    s = layer.spec
+    spec, fold_pad = _dgrad_spec(layer, seg_c)
+    if nsrc == 1 and s.cout == 1 and ops.final_dgrad_k7_ok(s, g, f):
+        return 'final_k7', fold_pad        # the generator's last layer in plain-bf16 arithmetic: the padded gradient on the bf16 matrix pipe
+    if nsrc == 1 and s.cout == 1 and ops.head_dgrad_ok(s, g, f):
+        return 'head', fold_pad            # the PatchGAN's output layer in plain-bf16 arithmetic: its gradient as an output stream
+    if fold_pad and ops.dgrad_strip_eligible(spec, g):
+        return 'strip', fold_pad           # 66-column padded gradient: two whole tile columns + a transposed 2-column strip
+    return 'conv', fold_pad
+
+
+def _split_operands(layer, out, pads, w_grad, xs_ok, geom, dgrad):
+    """Can the InstanceNorm backward of ``out`` write the operands of its consumers itself (ops.instnorm_bwd_split)?  Yes when every
+    consumer of the gradient is a bf16 matrix kernel: the weight gradient takes the gradient's split copy (xs_ok) or a prepared
+    M-role operand (ops.wgrad_gt_dims) and each data gradient stages split copies.  Returns (gt_dims, want_xs) or None."""
+    s = layer.spec
+    if (s.transposed or s.precision == ops.PRECISION_FP32 or ops.DEFAULT_PRECISION == ops.PRECISION_FP32 or (pads and pads[-1] > 1) or
+            not ops.instnorm_bwd_split_ok(out, 1 if pads else 0)):
         return None
     gt_dims = None
-    wg_xs = False
-    if layer.weight.requires_grad:
-        # split-bf16 3x3 layers whose sources carry their forward copies: the weight gradient reads the gradient's split copy itself
-        # (ops.wgrad g_xs=, ap_conv2d_wgrad_xs) -- no prepared operand; plain bf16 keeps the prepared-operand kernel (faster there)
-        wg_xs = (s.precision == ops.PRECISION_BF16X3 and ops.DEFAULT_PRECISION == ops.PRECISION_BF16X3 and
-                 ops.wgrad_xs_ok(s.k, s.stride, s.pad, s.pad_mode, (n, c, h, w), srcs, s.precision))
-        if not wg_xs:
-            gt_dims = ops.wgrad_gt_dims(s.k, s.stride, s.pad, s.pad_mode, (n, c, h, w), srcs, s.precision)
-            if gt_dims is None:
-                return None
-    want_xs = want_strip = False
-    probe = Feat(out.data)                 # a plain feature of the gradient's shape
-    for i, f in enumerate(srcs):
-        if tape.tracked(f):
-            spec, fold_pad = _dgrad_spec(layer, s.cin_segments[i])
-            if not ops.takes_split(spec, n, h, w):
-                return None
-            want_xs = True
-            want_strip = want_strip or bool(fold_pad and ops.dgrad_strip_eligible(spec, probe))
-    if gt_dims is None and not want_xs and not wg_xs:
+    if w_grad and not xs_ok:
+        gt_dims = ops.wgrad_gt_dims(*geom)
+        if gt_dims is None:
+            return None
+    n, _, h, w = out.shape
+    if not all(d is None or ops.takes_split(_dgrad_spec(layer, c)[0], n, h, w) for c, d in zip(s.cin_segments, dgrad)):
         return None
-    return gt_dims, want_xs or wg_xs, want_strip, wg_xs
+    want_xs = any(d is not None for d in dgrad)
+    return (gt_dims, want_xs or xs_ok) if (w_grad or want_xs) else None
 
 
 def conv_backward(tape, layer, srcs, out, norm, act):
@@ -206,83 +239,82 @@ def conv_backward(tape, layer, srcs, out, norm, act):
     contribs = tape.take(out)
     if not contribs:
         return
-    s = layer.spec
-    gt = strip = g_xs = db = None
-    plan = _split_backward_plan(tape, layer, srcs, out, contribs) if norm else None
-    if plan is not None:
-        # the gradient only feeds the bf16 matrix kernels: its producer writes their operands, no fp32 dy (ops.instnorm_bwd_split)
-        red, gt_dims, want_xs, want_strip, wg_xs = plan
-        gfeat, gt, strip = ops.instnorm_bwd_split(red, out, gt_dims, want_xs, want_strip)
-        g_xs = gfeat.xs if wg_xs else None
-        dy = None
+    plan = _backward_plan(tape, layer, srcs, out, norm, act, contribs)
+    gfeat, gt, strip, db = _backward_norm(tape, plan, layer, out, act, contribs)
+    _backward_weight(tape, plan, layer, srcs, gfeat, gt)
+    _backward_bias(tape, layer, norm, gfeat, db)
+    _backward_data(tape, plan, layer, srcs, gfeat, strip)
+
+
+def _backward_norm(tape, plan, layer, out, act, contribs):
+    """The gradient w.r.t. the raw convolution output as (Feat, prepared M-role operand, column strip, bias gradient); the last
+    three None where the route does not make them."""
+    if plan.norm_route == 'split':
+        return ops.instnorm_bwd_split(ops._split_contribs(contribs), out, plan.gt_dims, plan.want_xs, plan.want_strip) + (None,)
+    if out.data.dtype != torch.float32:      # (a bf16 raw output whose backward takes the fp32 route after all: convert once)
+        out = Feat(out.data.float(), out._mean, out._rstd, out.act)
+        contribs = [(g.float() if g.dtype != torch.float32 else g, pd) for g, pd in contribs]
+    db = None
+    if plan.norm_route == 'instnorm':
+        dy = ops.instnorm_bwd(contribs, out, out_bf16=plan.dy16)
+    elif plan.norm_route == 'act_bias':
+        # a plain layer with an activation (the PatchGAN's first): the bias gradient's block sums are formed while dy is written
+        dy, db = ops.act_bwd_bias(contribs, out.data, act, tape.slot(layer.bias))
     else:
-        if out.data.dtype != torch.float32:      # (a bf16 raw output whose backward takes the fp32 route after all: convert once)
-            out = Feat(out.data.float(), out._mean, out._rstd, out.act)
-            contribs = [(g.float() if g.dtype != torch.float32 else g, pd) for g, pd in contribs]
-        # a stem (no data gradient: its input is an image) whose weight gradient runs on the bf16 matrix pipe: dy has one reader,
-        # which rounds it to bf16 -- it is stored that way (ops.instnorm_bwd out_bf16)
-        dy16 = (norm and layer.weight.requires_grad and not any(tape.tracked(f) for f in srcs) and
-                ops.k7_stem_wgrad_ok(s, tuple(out.data.shape), srcs))
-        if norm:
-            dy = ops.instnorm_bwd(contribs, out, out_bf16=dy16)
-        elif layer.bias.requires_grad and act != ACT_NONE:
-            # a plain layer with an activation (the PatchGAN's first): the bias gradient's block sums are formed while dy is written
-            dy, db = ops.act_bwd_bias(contribs, out.data, act, tape.slot(layer.bias))
-        else:
-            dy = ops.act_bwd(contribs, out.data, act)
-        gfeat = Feat(dy)
-        # split-bf16 layers served by ap_conv2d_wgrad_xs (3x3, the PatchGAN's 4x4): the gradient's split copy -- which the data-gradient
-        # convolution stages anyway (cached on the Feat) -- is the weight gradient's operand too: no operand preparation
-        if (layer.weight.requires_grad and not s.transposed and s.precision == ops.PRECISION_BF16X3 and
-                ops.DEFAULT_PRECISION == ops.PRECISION_BF16X3 and dy.shape[1] % 8 == 0 and
-                ops.wgrad_xs_ok(s.k, s.stride, s.pad, s.pad_mode, tuple(dy.shape), srcs, s.precision)):
-            g_xs = ops.presplit(gfeat, s.precision)
-    # ---- weight gradient
-    if layer.weight.requires_grad:
-        if s.transposed:
-            # dW[ci][co*k*k]: M-role = the layer input (virtual allowed), shifted tensor = dy (stride 2)
-            dw = ops.wgrad(s.k, 2, s.pad, PAD_ZERO, srcs[0], [gfeat], layer.weight.shape, precision=s.precision,
-                           out=tape.slot(layer.weight))
-        else:
-            dw = ops.wgrad(s.k, s.stride, s.pad, s.pad_mode, gfeat, srcs, layer.weight.shape, precision=s.precision,
-                           out=tape.slot(layer.weight), g_t=gt, g_xs=g_xs)
-        tape.add_param(layer.weight, dw)
-    if layer.bias.requires_grad:
-        # a bias in front of InstanceNorm has an exactly-zero gradient (it is removed by the mean subtraction)
-        slot = tape.slot(layer.bias)
-        if norm:
-            tape.add_param(layer.bias, slot if slot is not None else torch.zeros_like(layer.bias))   # block is zero-filled
-        else:
-            tape.add_param(layer.bias, db if db is not None else ops.bias_grad(dy, out=slot))
-    # ---- data gradients, one launch per input segment that needs one
+        dy = ops.act_bwd(contribs, out.data, act)
+    gfeat = Feat(dy)
+    if plan.wgrad_operand == 'g_xs_presplit':
+        ops.presplit(gfeat, layer.spec.precision)
+    return gfeat, None, None, db
+
+
+def _backward_weight(tape, plan, layer, srcs, gfeat, gt):
+    if plan.wgrad_route is None:
+        return
+    s = layer.spec
+    if s.transposed:
+        dw = ops.wgrad(s.k, 2, s.pad, PAD_ZERO, srcs[0], [gfeat], layer.weight.shape, precision=s.precision,
+                       out=tape.slot(layer.weight), route=plan.wgrad_route)
+    else:
+        g_xs = gfeat.xs if plan.wgrad_operand in ('g_xs_from_split', 'g_xs_presplit') else None
+        dw = ops.wgrad(s.k, s.stride, s.pad, s.pad_mode, gfeat, srcs, layer.weight.shape, precision=s.precision,
+                       out=tape.slot(layer.weight), g_t=gt, g_xs=g_xs, route=plan.wgrad_route)
+    tape.add_param(layer.weight, dw)
+
+
+def _backward_bias(tape, layer, norm, gfeat, db):
+    if not layer.bias.requires_grad:
+        return
+    slot = tape.slot(layer.bias)
+    if norm:     # a bias in front of InstanceNorm has an exactly-zero gradient (it is removed by the mean subtraction)
+        tape.add_param(layer.bias, slot if slot is not None else torch.zeros_like(layer.bias))   # block is zero-filled
+    else:
+        tape.add_param(layer.bias, db if db is not None else ops.bias_grad(gfeat.data, out=slot))
+
+
+def _backward_data(tape, plan, layer, srcs, gfeat, strip):
+    """One launch (the strip route: two) per input segment that needs a gradient."""
+    s = layer.spec
     c0 = 0
-    for i, f in enumerate(srcs):
-        c = s.cin_segments[i]
-        if tape.tracked(f):
-            spec, fold_pad = _dgrad_spec(layer, c)
-            if len(srcs) == 1 and s.cout == 1 and ops.final_dgrad_k7_ok(s, gfeat, f):
-                # the generator's last layer in plain-bf16 arithmetic: the padded gradient on the bf16 matrix pipe (dgrad_k7.h)
-                tape.add(f, ops.final_dgrad_k7(gfeat, layer.weight), fold_pad)
-                c0 += c
-                continue
-            if len(srcs) == 1 and s.cout == 1 and ops.head_dgrad_ok(s, gfeat, f):
-                # the PatchGAN's output layer in plain-bf16 arithmetic: its 512-channel gradient as an output stream (dgrad_k7.h)
-                tape.add(f, ops.head_dgrad(gfeat, layer.weight, f.data.shape[2], f.data.shape[3]), fold_pad)
-                c0 += c
-                continue
+    for i, (f, c, route) in enumerate(zip(srcs, s.cin_segments, plan.dgrad)):
+        if route is not None and route[0] == 'final_k7':
+            tape.add(f, ops.final_dgrad_k7(gfeat, layer.weight), route[1])
+        elif route is not None and route[0] == 'head':
+            tape.add(f, ops.head_dgrad(gfeat, layer.weight, f.data.shape[2], f.data.shape[3]), route[1])
+        elif route is not None:
+            spec, _ = _dgrad_spec(layer, c)
             w = layer.weight.detach()
             if len(srcs) > 1:
                 w = w[c0:c0 + c] if s.transposed else w[:, c0:c0 + c]       # a view: the packer takes strides
             packed = layer.packed_dgrad(i, spec, w)
-            if fold_pad and ops.dgrad_strip_eligible(spec, gfeat):
-                # 66-column padded gradient: two whole tile columns + a transposed 2-column strip (ops.conv2d_dgrad_strip)
+            if route[0] == 'strip':
                 packed_t = layer.packed_dgrad((i, 'T'), spec, w.transpose(2, 3))
                 # (a source whose raw output is stored as bf16 has this gradient as its ONLY contribution and its InstanceNorm
                 # backward on the operand-writing route: the gradient is stored as bf16 too)
                 g = ops.conv2d_dgrad_strip(spec, gfeat, packed, packed_t, strip, out_bf16=f.data.dtype == torch.bfloat16)
             else:
                 g = ops.conv2d(spec, [gfeat], packed, None).data
-            tape.add(f, g, fold_pad)
+            tape.add(f, g, route[1])
         c0 += c
 
 

@@ -1050,6 +1050,20 @@ static int fold_args_ok(const float* g1, int p1, int H, int W, const char* who) 
     return AP_OK;
 }
 
+// the one-workgroup-per-plane InstanceNorm backward with NT threads: the load-phase forms where the gradient comes in whole
+// 16-byte groups (unfolded / pad-1 fold, with or without a second contribution), else the general one
+template <int NT>
+static void launch_instnorm_bwd_fused(bool plain_vec, bool fold1_vec, const float* g1, int g1_pad, const float* g2, const float* y,
+                                      const float* mean, const float* rstd, int act, int NC, int H, int W, float* dy, ap_stream_t stream) {
+    const dim3 grid(NC), block(NT);
+    hipStream_t st = (hipStream_t)stream;
+    if (plain_vec && g2) hipLaunchKernelGGL((instnorm_bwd_fused_vec_kernel<NT, 16, true>), grid, block, 0, st, g1, g2, y, mean, rstd, act, H * W, dy);
+    else if (plain_vec) hipLaunchKernelGGL((instnorm_bwd_fused_vec_kernel<NT, 16, false>), grid, block, 0, st, g1, g2, y, mean, rstd, act, H * W, dy);
+    else if (fold1_vec && g2) hipLaunchKernelGGL((instnorm_bwd_fused_fold1_kernel<NT, 16, true>), grid, block, 0, st, g1, g2, y, mean, rstd, act, H, W, dy);
+    else if (fold1_vec) hipLaunchKernelGGL((instnorm_bwd_fused_fold1_kernel<NT, 16, false>), grid, block, 0, st, g1, g2, y, mean, rstd, act, H, W, dy);
+    else hipLaunchKernelGGL((instnorm_bwd_fused_kernel<NT, 16>), grid, block, 0, st, g1, g1_pad, g2, y, mean, rstd, act, H, W, dy);
+}
+
 extern "C" {
 
 int ap_instnorm_bwd(const float* g1, int32_t g1_pad, const float* g2, const float* y, const float* mean,
@@ -1064,46 +1078,25 @@ int ap_instnorm_bwd(const float* g1, int32_t g1_pad, const float* g2, const floa
     if (NC < 1 || NC > 65535) return fail(AP_ERR_UNSUPPORTED, "instnorm_bwd: N*C=%d", NC);
     if (ob16 && !(g1_pad == 0 && H * W > 16384 && H * W <= 65536 && (W % 4) == 0))
         return fail(AP_ERR_UNSUPPORTED, "instnorm_bwd: a bf16 dy is written by the big-plane kernel only (%dx%d, fold %d)", H, W, g1_pad);
-    constexpr bool fused_ok = true;
     const bool plain_vec = g1_pad == 0 && ((H * W) & 3) == 0;     // unfolded gradient, whole 16-byte groups: the load-phase form
     const bool fold1_vec = g1_pad == 1 && (W & 3) == 0 && H >= 3 && W >= 8;   // pad-1 fold, the same
-    if (fused_ok && g1_pad == 0 && H * W <= 1024 && ((H * W) & 3) != 0) {      // small planes that are not whole 16-byte groups
+    if (g1_pad == 0 && H * W <= 1024 && ((H * W) & 3) != 0) {      // small planes that are not whole 16-byte groups
         if (g2) hipLaunchKernelGGL(instnorm_bwd_fused_small_kernel<true>, dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H * W, dy);
         else hipLaunchKernelGGL(instnorm_bwd_fused_small_kernel<false>, dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H * W, dy);
         return check_launch("instnorm_bwd_fused_small_kernel");
     }
-    if (fused_ok && H * W <= 4096) {
-        if (plain_vec && g2) hipLaunchKernelGGL((instnorm_bwd_fused_vec_kernel<256, 16, true>), dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H * W, dy);
-        else if (plain_vec) hipLaunchKernelGGL((instnorm_bwd_fused_vec_kernel<256, 16, false>), dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H * W, dy);
-        else if (fold1_vec && g2) hipLaunchKernelGGL((instnorm_bwd_fused_fold1_kernel<256, 16, true>), dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H, W, dy);
-        else if (fold1_vec) hipLaunchKernelGGL((instnorm_bwd_fused_fold1_kernel<256, 16, false>), dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H, W, dy);
-        else hipLaunchKernelGGL((instnorm_bwd_fused_kernel<256, 16>), dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g1_pad, g2,
-                                y, mean, rstd, act, H, W, dy);
+    if (H * W <= 16384) {
+        if (H * W <= 4096) launch_instnorm_bwd_fused<256>(plain_vec, fold1_vec, g1, g1_pad, g2, y, mean, rstd, act, NC, H, W, dy, stream);
+        else launch_instnorm_bwd_fused<1024>(plain_vec, fold1_vec, g1, g1_pad, g2, y, mean, rstd, act, NC, H, W, dy, stream);
         return check_launch("instnorm_bwd_fused_kernel");
     }
-    if (fused_ok && H * W <= 16384) {
-        if (plain_vec && g2) hipLaunchKernelGGL((instnorm_bwd_fused_vec_kernel<1024, 16, true>), dim3(NC), dim3(1024), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H * W, dy);
-        else if (plain_vec) hipLaunchKernelGGL((instnorm_bwd_fused_vec_kernel<1024, 16, false>), dim3(NC), dim3(1024), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H * W, dy);
-        else if (fold1_vec && g2) hipLaunchKernelGGL((instnorm_bwd_fused_fold1_kernel<1024, 16, true>), dim3(NC), dim3(1024), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H, W, dy);
-        else if (fold1_vec) hipLaunchKernelGGL((instnorm_bwd_fused_fold1_kernel<1024, 16, false>), dim3(NC), dim3(1024), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H, W, dy);
-        else hipLaunchKernelGGL((instnorm_bwd_fused_kernel<1024, 16>), dim3(NC), dim3(1024), 0, (hipStream_t)stream, g1, g1_pad,
-                                g2, y, mean, rstd, act, H, W, dy);
-        return check_launch("instnorm_bwd_fused_kernel");
-    }
-    if (fused_ok && H * W <= 65536 && (W % 4) == 0 && W >= 4) {
-        static bool attr = false;
+    if (H * W <= 65536 && (W % 4) == 0 && W >= 4) {
         const size_t lds = 8 * 1024 * sizeof(float4);
-        if (!attr) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&instnorm_bwd_fused_big_kernel<false>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&instnorm_bwd_fused_big_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&instnorm_bwd_fused_big_kernel<false, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr = true;
+        for (const void* fn : {reinterpret_cast<const void*>(&instnorm_bwd_fused_big_kernel<false>),
+                               reinterpret_cast<const void*>(&instnorm_bwd_fused_big_kernel<true>),
+                               reinterpret_cast<const void*>(&instnorm_bwd_fused_big_kernel<false, true>)}) {
+            rc = ensure_dyn_lds(fn, (int)lds);
+            if (rc) return rc;
         }
         if (ob16)
             hipLaunchKernelGGL((instnorm_bwd_fused_big_kernel<false, true>), dim3(NC), dim3(1024), lds, (hipStream_t)stream, g1, g1_pad,
@@ -1162,16 +1155,9 @@ int ap_instnorm_bwd_split(const float* g1, int32_t g1_pad, const float* g2, cons
     p.strip = strip; p.dy = dy; p.heads_only = (heads_only & 1) ? 1 : 0;
     const bool yb16 = (heads_only & 2) != 0, g16 = (heads_only & 4) != 0;
     p.N = N;
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(AP_ERR_LAUNCH, "instnorm_bwd_split: no device");
-        cus = prop.multiProcessorCount;
-    }
     const int items = N * (C / 8);
     const bool small = H * W / 4 <= 256;
-    const int slots = cus * (small ? 4 : 1);          // resident workgroups: registers hold one 1024-thread item per CU, four of 256
+    const int slots = num_cus() * (small ? 4 : 1);          // resident workgroups: registers hold one 1024-thread item per CU, four of 256
     const dim3 grid(items < slots ? items : slots);
     auto launch = [&](auto nt) {
         constexpr int NTH = decltype(nt)::value;

@@ -6,6 +6,7 @@ activation that the CONSUMER applies while it stages the tensor into LDS.  This 
 ``Conv2d -> InstanceNorm2d -> ReLU`` chains of the reference
 (Module2/models/networks.py:1218-1282) run as one kernel per convolution.
 """
+import collections
 import ctypes
 import os
 
@@ -117,6 +118,10 @@ class Feat:
     def shape(self):
         return self.data.shape
 
+    @property
+    def dtype(self):
+        return self.data.dtype
+
     @classmethod
     def split_only(cls, shape, xs):
         """A feature that exists only as its split-bf16 copy (inference: the fp32 tensor is never written).
@@ -173,6 +178,18 @@ class Feat:
         c = self.data.shape[1]
         return Feat(self.data[lo:hi], None if self.mean is None else self.mean[lo * c:hi * c],
                     None if self.rstd is None else self.rstd[lo * c:hi * c], self.act)
+
+
+# What a backward route decision may read of a feature -- shapes, dtypes and presence flags, never memory -- under the names Feat
+# gives them, so that a predicate takes either (xs, s2d: whether that copy exists)
+Form = collections.namedtuple('Form', 'shape dtype virtual act xs s2d is_split_only xs_heads_only')
+
+
+def form_of(f):
+    if isinstance(f, Form):
+        return f
+    return Form(tuple(f.data.shape), f.data.dtype, f.virtual, f.act, f.xs is not None, f.s2d is not None and f.s2d.xs is not None,
+                f.is_split_only, f.xs_heads_only)
 
 
 class ConvSpec:
@@ -762,12 +779,12 @@ def _conv2d_view(spec, srcs, packed, out, view):
 
 def dgrad_strip_eligible(spec, g):
     """spec: data-gradient operator of a reflection-padded 3x3 stride-1 layer (full correlation, pad 2), g: the plain
-    gradient Feat.  True when the padded-coordinate output is 32 m + 2 columns wide (the 64 x 64 maps of the ResNet
+    gradient Feat (or its form).  True when the padded-coordinate output is 32 m + 2 columns wide (the 64 x 64 maps of the ResNet
     blocks: 66) and the operator runs on the split-bf16 path: see conv2d_dgrad_strip."""
     if (spec.precision == PRECISION_FP32 or spec.k != 3 or spec.stride != 1 or spec.pad != 2 or spec.transposed or
             len(spec.cin_segments) != 1 or g.virtual):
         return False
-    n, c, h, w = g.data.shape
+    n, c, h, w = g.shape
     if (w + 2) % 32 != 2 or w < 32 or h < 4 or c % 8:
         return False
     d = spec.desc(n, h, w, None, ACT_NONE)
@@ -924,7 +941,60 @@ def _wgrad_buffers(nfloats, what, out, out_shape, device):
     return ws, _grad_out(out, out_shape, device)
 
 
-def wgrad(k, stride, pad, pad_mode, g, srcs, out_shape, precision=None, out=None, g_t=None, g_xs=None):
+# Everything the backward route decisions read besides the forms of the tensors (form_of): the module switches and the environment
+# variables the C side reads per call for its plan queries (wgrad_host.hip: make_wgrad_plan, the xs predicates; conv_host.hip:
+# make_plan behind ap_conv2d_wants_presplit; ap_instnorm_bwd_split_ok) and s2d_eligible reads here.  Tests and A/B runs flip them
+# inside one process: every cached decision is keyed by backward_switches().  A new switch of a backward route is listed HERE.
+_WGRAD_XS_ENV = ('APAMD_NO_XS_DIRECT', 'APAMD_NO_XS_WGRAD', 'APAMD_NO_BF16X3', 'APAMD_NO_S2D_WGRAD', 'APAMD_ROWS_WGRAD',
+                 'APAMD_NO_INBWD_SPLIT', 'APAMD_NO_S2D', 'APAMD_NO_SMALL', 'APAMD_NO_SMALL_TILES')
+
+
+def backward_switches():
+    return (DEFAULT_PRECISION, XS_WGRAD, XS_DIRECT, K7_WGRAD, D0_MFMA, BF16_RAW) + tuple(os.environ.get(v) for v in _WGRAD_XS_ENV)
+
+
+# (k, stride, pad, pad_mode) of the edge layers that have kernels of their own
+K7_EDGE = (7, 1, 3, PAD_REFLECT)     # the generator's stems and its last layer
+D0_EDGE = (4, 2, 1, PAD_ZERO)        # the PatchGAN's first layer
+HEAD_EDGE = (4, 1, 1, PAD_ZERO)      # the PatchGAN's output layer
+
+
+def _plain_bf16_layer(spec, geom):
+    """A layer of this geometry in plain-bf16 arithmetic while that is the package mode too: what the bf16 edge kernels serve."""
+    return (DEFAULT_PRECISION == PRECISION_BF16 and spec.precision == PRECISION_BF16 and not spec.transposed and
+            (spec.k, spec.stride, spec.pad, spec.pad_mode) == geom)
+
+
+def wgrad_route(k, stride, pad, pad_mode, g_form, src_forms, out_shape, precision, prepared):
+    """The kernel family that serves a weight gradient, from forms alone (form_of; prepared: the M-role operand comes as g_t / g_xs).
+    The edge layers have kernels of their own; they are tried first, in this order, with their C-side shape queries: a chosen
+    route does not decline."""
+    geom, f = (k, stride, pad, pad_mode), src_forms[0]
+    n, m, gh, gw = g_form.shape
+    cin, (h, w) = sum(s.shape[1] for s in src_forms), f.shape[2:]
+    one_src, plain_g, plain_f = len(src_forms) == 1, not g_form.virtual and g_form.act == ACT_NONE, not f.virtual and f.act == ACT_NONE
+    oihw = tuple(out_shape) == (m, cin, k, k)
+    if m == 1 and geom == HEAD_EDGE and one_src and cin >= 64 and plain_g and oihw and h <= 32 and w <= 31:
+        return 'head'
+    # (the bf16 weight-gradient kernels ask for the layer's precision only, the other bf16 edge kernels for the package mode too)
+    bf16_own = precision == PRECISION_BF16 and one_src and not prepared and plain_g and f.dtype == torch.float32 and oihw
+    if K7_WGRAD and bf16_own and geom == K7_EDGE:
+        if m == 1 and cin >= 32:         # the last layer: wide = the input
+            if g_form.dtype == torch.float32 and C.lib().ap_wgrad_k7_bf16_ok(n, cin, m, h, w, 1) == 1:
+                return 'k7_final'
+        elif plain_f and C.lib().ap_wgrad_k7_bf16_ok(n, m, cin, h, w, 0) == 1:
+            return 'k7_stem'
+    if (D0_MFMA and bf16_own and geom == D0_EDGE and plain_f and not f.is_split_only and (gh, gw) == (h // 2, w // 2) and
+            C.lib().ap_wgrad_d0_bf16_ok(n, m, cin, h, w) == 1):
+        return 'd0'
+    if m == 1 and geom[:3] == K7_EDGE[:3] and one_src and cin >= 16 and plain_g and oihw:
+        return 'final'
+    if m <= 4 and stride == 1 and cin >= 16 and oihw and 2 * pad == k - 1:
+        return 'few_outputs'
+    return 'general'
+
+
+def wgrad(k, stride, pad, pad_mode, g, srcs, out_shape, precision=None, out=None, g_t=None, g_xs=None, route=None):
     """Weight gradient (see include/animateportrait_amd.h: ap_conv2d_wgrad).  g: Feat of the M-role tensor,
     srcs: Feats of the shifted tensor's segments.  Returns a tensor of ``out_shape`` (OIHW / IOHW): ``out`` when given
     (the layer's slot in the network's contiguous gradient block), else a new tensor.
@@ -932,37 +1002,22 @@ def wgrad(k, stride, pad, pad_mode, g, srcs, out_shape, precision=None, out=None
     g_t: the M-role operand as instnorm_bwd_split wrote it (wgrad_gt_dims); ``g`` then only carries the shape.
     g_xs: the split copy of the gradient (instnorm_bwd_split's ``xs``): where the layer is served by ap_conv2d_wgrad_xs (both operands
     read as the convolutions' split copies, no preparation) that route is taken; ``g`` again only carries the shape.
-    The edge layers have kernels of their own; they are tried first, in this order."""
-    m = g.data.shape[1]
-    cin = sum(f.data.shape[1] for f in srcs)
-    prec = DEFAULT_PRECISION if precision is None else precision
-    one_src, own_g, plain_g = len(srcs) == 1, g_t is None and g_xs is None, not g.virtual and g.act == ACT_NONE
-    oihw = tuple(out_shape) == (m, cin, k, k)
-    if (m == 1 and k == 4 and stride == 1 and one_src and cin >= 64 and plain_g and oihw and srcs[0].data.shape[2] <= 32 and
-            srcs[0].data.shape[3] <= 31 and pad == 1 and pad_mode == PAD_ZERO):
-        return _wgrad_head(k, pad, g, srcs[0], out_shape, out)
-    if (K7_WGRAD and prec == PRECISION_BF16 and k == 7 and stride == 1 and pad == 3 and pad_mode == PAD_REFLECT and one_src and
-            own_g and plain_g and srcs[0].data.dtype == torch.float32):
-        dw = _wgrad_k7(k, g, srcs[0], out_shape, out)
-        if dw is not None:
-            return dw
-    if g.data.dtype == torch.bfloat16 and own_g:
+    route: what wgrad_route answers for this call, when the caller has asked already (the layer's backward plan)."""
+    own_g = g_t is None and g_xs is None
+    if route is None:
+        route = wgrad_route(k, stride, pad, pad_mode, form_of(g), [form_of(f) for f in srcs], out_shape,
+                            DEFAULT_PRECISION if precision is None else precision, not own_g)
+    if g.data.dtype == torch.bfloat16 and own_g and route not in ('k7_stem', 'k7_final'):
         g = Feat(g.data.float(), g._mean, g._rstd, g.act)       # (only wgrad_k7 reads a bf16-stored gradient)
-    if (D0_MFMA and prec == PRECISION_BF16 and k == 4 and stride == 2 and pad == 1 and pad_mode == PAD_ZERO and one_src and
-            own_g and plain_g and not srcs[0].virtual and srcs[0].act == ACT_NONE and not srcs[0].is_split_only and
-            srcs[0].data.dtype == torch.float32 and oihw):
-        dw = _wgrad_d0(g, srcs[0], out_shape, out)
-        if dw is not None:
-            return dw
-    if m == 1 and k == 7 and stride == 1 and pad == 3 and one_src and cin >= 16 and plain_g and oihw:
-        return _wgrad_final(k, pad, pad_mode, g, srcs[0], out_shape, out)
-    if m <= 4 and stride == 1 and cin >= 16 and oihw and 2 * pad == k - 1:
+    if route == 'general':
+        return _wgrad_general(k, stride, pad, pad_mode, g, srcs, out_shape, precision, out, g_t, g_xs)
+    if route == 'few_outputs':
         dw = _wgrad_few_outputs(k, pad, pad_mode, g, srcs, out_shape)
         return dw if out is None else out.copy_(dw)
-    return _wgrad_general(k, stride, pad, pad_mode, g, srcs, out_shape, precision, out, g_t, g_xs)
+    return _WGRAD_EDGE[route](k, pad, pad_mode, g, srcs[0], out_shape, out)
 
 
-def _wgrad_head(k, pad, g, f, out_shape, out):
+def _wgrad_head(k, pad, pad_mode, g, f, out_shape, out):
     """PatchGAN output layer: one workgroup per input channel (conv_head.h)"""
     _require_device(f.data, 'wgrad source')
     _require_device(g.data, 'wgrad gradient')
@@ -973,17 +1028,13 @@ def _wgrad_head(k, pad, g, f, out_shape, out):
     return dw
 
 
-def _wgrad_k7(k, g, f, out_shape, out):
+def _wgrad_k7(k, pad, pad_mode, g, f, out_shape, out):
     """The 7x7 edge layers at full resolution, plain-bf16 arithmetic: one pass over the wide tensor on the bf16 matrix pipe
-    (wgrad_k7.h) -- the stems (wide = the gradient) and the last layer (wide = the input).  None: the shape is not served."""
+    (wgrad_k7.h) -- the stems (wide = the gradient) and the last layer (wide = the input)."""
     n, m = g.data.shape[:2]
     cin, h, w = f.data.shape[1:]
     final_form = 1 if (m == 1 and cin >= 32) else 0
     wide, narrow = (f, g) if final_form else (g, f)
-    if not ((final_form or not f.virtual and f.act == ACT_NONE) and tuple(out_shape) == (m, cin, k, k) and
-            (g.data.dtype == torch.float32 or not final_form) and
-            C.lib().ap_wgrad_k7_bf16_ok(n, wide.data.shape[1], narrow.data.shape[1], h, w, final_form) == 1):
-        return None
     _require_device(f.data, 'wgrad source')
     _require_device(g.data, 'wgrad gradient', allow_bf16=not final_form)
     sw = _src_of(wide, bf16_bit=True)       # (bf16: the stems' gradient as instnorm_bwd(out_bf16=True) stored it)
@@ -997,13 +1048,10 @@ def _wgrad_k7(k, g, f, out_shape, out):
     return dw
 
 
-def _wgrad_d0(g, f, out_shape, out):
-    """The PatchGAN's first layer, plain-bf16 arithmetic: one pass over the gradient on the bf16 matrix pipe (wgrad_k7.h, form 2).
-    None: the shape is not served."""
-    n, m, gh, gw = g.data.shape
+def _wgrad_d0(k, pad, pad_mode, g, f, out_shape, out):
+    """The PatchGAN's first layer, plain-bf16 arithmetic: one pass over the gradient on the bf16 matrix pipe (wgrad_k7.h, form 2)."""
+    n, m = g.data.shape[:2]
     cin, h, w = f.data.shape[1:]
-    if (gh, gw) != (h // 2, w // 2) or C.lib().ap_wgrad_d0_bf16_ok(n, m, cin, h, w) != 1:
-        return None
     _require_device(f.data, 'wgrad source')
     _require_device(g.data, 'wgrad gradient')
     ws, dw = _wgrad_buffers(C.lib().ap_wgrad_d0_bf16_workspace_floats(n, m, cin, h, w), 'wgrad_d0_ws', out, out_shape, g.data.device)
@@ -1025,6 +1073,9 @@ def _wgrad_final(k, pad, pad_mode, g, f, out_shape, out):
     C.check(C.lib().ap_conv_final_wgrad(ctypes.byref(s), _ptr(g.data), n, h, w, k, pad, pad_mode, _ptr(ws), _ptr(dw),
                                         _stream()), 'conv_final_wgrad')
     return dw
+
+
+_WGRAD_EDGE = {'head': _wgrad_head, 'k7_stem': _wgrad_k7, 'k7_final': _wgrad_k7, 'd0': _wgrad_d0, 'final': _wgrad_final}
 
 
 def _wgrad_general(k, stride, pad, pad_mode, g, srcs, out_shape, precision, out, g_t, g_xs):
@@ -1051,63 +1102,78 @@ def _wgrad_general(k, stride, pad, pad_mode, g, srcs, out_shape, precision, out,
     return dw
 
 
-def _wgrad_desc(k, stride, pad, pad_mode, g_shape, g, srcs, precision):
-    """ap_wgrad_desc of a layer; g None: the M-role operand comes prepared (ap_conv2d_wgrad_pre) and its pointers stay empty."""
+_SOME_POINTER = 0x1000      # the planner only asks whether a pointer is null
+
+
+def _wgrad_plan_desc(k, stride, pad, pad_mode, g_shape, src_forms, precision):
+    """ap_wgrad_desc of a layer for the plan queries, from the forms of its sources: every pointer a Feat would fill is a stand-in."""
     n, m, gh, gw = g_shape
     d = C.ApWgradDesc()
     d.N, d.M, d.GH, d.GW = n, m, gh, gw
-    d.H, d.W = srcs[0].data.shape[2], srcs[0].data.shape[3]
+    d.H, d.W = src_forms[0].shape[2:]
     d.K, d.stride, d.pad, d.pad_mode = k, stride, pad, pad_mode
-    d.nsrc = len(srcs)
+    d.nsrc = len(src_forms)
     d.precision = DEFAULT_PRECISION if precision is None else precision
     d.g.C, d.g.act = m, ACT_NONE
+    for i, f in enumerate(src_forms):
+        stats = _SOME_POINTER if f.virtual else None
+        d.src[i] = C.ApSrc(_SOME_POINTER, stats, stats, f.shape[1], f.act | (0x100 if f.dtype == torch.bfloat16 else 0))
+    # the split copies the forward pass staged of the same sources (still alive on the tape): the C side re-tiles the shifted
+    # operand from them instead of normalising + splitting the fp32 tensors again (ap_wgrad_desc.src_xs)
+    if XS_WGRAD:
+        heads = DEFAULT_PRECISION == PRECISION_BF16 or any(f.xs_heads_only for f in src_forms)
+        d.xs_parts = 1 if heads else 2
+        if all(f.xs for f in src_forms):
+            for i in range(len(src_forms)):
+                d.src_xs[i] = _SOME_POINTER
+        if len(src_forms) == 1 and src_forms[0].s2d:
+            d.src_xs_s2d = _SOME_POINTER
+    return d
+
+
+def _wgrad_desc(k, stride, pad, pad_mode, g_shape, g, srcs, precision):
+    """ap_wgrad_desc of a layer; g None: the M-role operand comes prepared (ap_conv2d_wgrad_pre) and its pointers stay empty."""
+    d = _wgrad_plan_desc(k, stride, pad, pad_mode, g_shape, [form_of(f) for f in srcs], precision)
     if g is not None:
         _require_device(g.data, 'wgrad gradient')
         d.g = _src_of(g)
     for i, f in enumerate(srcs):
         _require_device(f.data, 'wgrad source', allow_bf16=True)
         d.src[i] = _src_of(f, bf16_bit=True)       # (the C side refuses bf16 values where its kernels cannot read them)
-    # the split copies the forward pass staged of the same sources (still alive on the tape): the C side re-tiles the shifted
-    # operand from them instead of normalising + splitting the fp32 tensors again (ap_wgrad_desc.src_xs)
-    if XS_WGRAD:
-        heads = DEFAULT_PRECISION == PRECISION_BF16 or any(f.xs_heads_only for f in srcs)
-        d.xs_parts = 1 if heads else 2
-        if all(f.xs is not None for f in srcs):
-            for i, f in enumerate(srcs):
-                d.src_xs[i] = f.xs.data_ptr()
-        if len(srcs) == 1 and srcs[0].s2d is not None and srcs[0].s2d.xs is not None:
-            d.src_xs_s2d = srcs[0].s2d.xs.data_ptr()
+        if d.src_xs[i]:
+            d.src_xs[i] = f.xs.data_ptr()
+    if d.src_xs_s2d:
+        d.src_xs_s2d = srcs[0].s2d.xs.data_ptr()
     return d
 
 
 def wgrad_xs_ok(k, stride, pad, pad_mode, g_shape, srcs, precision=None):
-    """Is this weight gradient served with both operands as split copies (ap_conv2d_wgrad_xs)?  Needs the sources' forward copies."""
+    """Is this weight gradient served with both operands as split copies (ap_conv2d_wgrad_xs)?  Needs the sources' forward copies.
+    srcs: Feats or their forms."""
     if not XS_DIRECT or g_shape[1] <= 4:
         return False
     # the answer depends on the layer geometry and on WHICH forward copies the sources carry, not on their contents: cached, so
     # that the backward pass of a launch-bound train step does not rebuild a descriptor and re-plan per layer and step (ADVICE r5).
-    # The key holds everything else the descriptor and the C-side plan read: the package mode (precision None, the head-only
-    # copies), the module switches, and the environment switches the library reads per call (tests and A/B runs flip them)
-    key = (k, stride, pad, pad_mode, tuple(g_shape), DEFAULT_PRECISION if precision is None else precision, DEFAULT_PRECISION,
-           XS_WGRAD, XS_DIRECT, tuple(os.environ.get(v) for v in _WGRAD_XS_ENV),
-           tuple((tuple(f.data.shape), f.xs is not None, f.s2d is not None, f.is_split_only, f.xs_heads_only) for f in srcs))
+    # The key holds everything else the descriptor and the C-side plan read (backward_switches)
+    forms = tuple(form_of(f) for f in srcs)
+    key = (k, stride, pad, pad_mode, tuple(g_shape), precision, backward_switches(), forms)
     hit = _WGRAD_XS_OK.get(key)
     if hit is None:
-        d = _wgrad_desc(k, stride, pad, pad_mode, g_shape, None, srcs, precision)
+        d = _wgrad_plan_desc(k, stride, pad, pad_mode, g_shape, forms, precision)
         hit = _WGRAD_XS_OK[key] = C.lib().ap_conv2d_wgrad_xs_ok(ctypes.byref(d)) == 1
     return hit
 
 
 _WGRAD_XS_OK = {}
-_WGRAD_XS_ENV = ('APAMD_NO_XS_DIRECT', 'APAMD_NO_XS_WGRAD', 'APAMD_NO_BF16X3', 'APAMD_NO_S2D_WGRAD', 'APAMD_ROWS_WGRAD')
 
 
 def wgrad_gt_dims(k, stride, pad, pad_mode, g_shape, srcs, precision=None):
     """(rows, pixel octets per row, padded channels) of the M-role operand when this weight gradient runs on the bf16 matrix kernel
-    and therefore takes the operand prepared by its producer (instnorm_bwd_split -> wgrad(..., g_t=)); None when it does not."""
+    and therefore takes the operand prepared by its producer (instnorm_bwd_split -> wgrad(..., g_t=)); None when it does not.
+    srcs: Feats or their forms."""
     if g_shape[1] <= 4:
         return None          # the narrow-output special cases of wgrad()
-    d = _wgrad_desc(k, stride, pad, pad_mode, g_shape, None, srcs, precision)
+    d = _wgrad_plan_desc(k, stride, pad, pad_mode, g_shape, [form_of(f) for f in srcs], precision)
     dims = (ctypes.c_int32 * 3)()
     if C.check(C.lib().ap_conv2d_wgrad_gt_dims(ctypes.byref(d), dims), 'wgrad_gt_dims') != 1:
         return None
@@ -1184,7 +1250,7 @@ def fold_add(g1, pad, g2):
 
 def instnorm_bwd(contribs, f, out_bf16=False):
     """Gradient w.r.t. the raw conv output y of the virtual feature f = act(IN(y)).
-    out_bf16: the caller's ONLY reader of dy is the stems' weight gradient on the bf16 matrix pipe (k7_stem_wgrad_ok): where the
+    out_bf16: the caller's ONLY reader of dy is the stems' weight gradient on the bf16 matrix pipe (wgrad_route 'k7_stem'): where the
     big-plane kernel serves the call, dy is stored as bf16 (half the bytes written and read back)."""
     g1, pad, g2 = _split_contribs(contribs)
     g1, g2 = _as_fp32_grad(g1), _as_fp32_grad(g2)
@@ -1200,8 +1266,7 @@ def instnorm_bwd(contribs, f, out_bf16=False):
 def conv_d0_ok(spec, srcs, act):
     """Is this layer the PatchGAN's first (1 | 2 -> 64 channels, 4x4 stride 2 on a plain image) in plain-bf16 arithmetic, served as
     an output stream on the bf16 matrix pipe (ap_conv_d0_fwd_bf16)?"""
-    if not (D0_MFMA and DEFAULT_PRECISION == PRECISION_BF16 and spec.precision == PRECISION_BF16 and not spec.transposed and
-            spec.k == 4 and spec.stride == 2 and spec.pad == 1 and spec.pad_mode == PAD_ZERO and len(srcs) == 1 and act in (ACT_NONE, ACT_RELU, ACT_LRELU)):
+    if not (D0_MFMA and _plain_bf16_layer(spec, D0_EDGE) and len(srcs) == 1 and act in (ACT_NONE, ACT_RELU, ACT_LRELU)):
         return False
     f = srcs[0]
     if f.is_split_only or f.virtual or f.act != ACT_NONE or f.data.dtype != torch.float32:
@@ -1223,12 +1288,12 @@ def conv_d0(f, weight, bias, act):
 
 
 def final_dgrad_k7_ok(spec, g, f):
-    """Is the data gradient of this layer the last layer's, served on the bf16 matrix pipe (ap_conv_final_dgrad_bf16)?"""
-    n, m, h, w = g.data.shape
-    return (K7_WGRAD and DEFAULT_PRECISION == PRECISION_BF16 and spec.precision == PRECISION_BF16 and not spec.transposed and
-            spec.k == 7 and spec.stride == 1 and spec.pad == 3 and spec.pad_mode == PAD_REFLECT and m == 1 and not g.virtual and
-            g.act == ACT_NONE and g.data.dtype == torch.float32 and tuple(f.data.shape[2:]) == (h, w) and
-            C.lib().ap_conv_final_dgrad_bf16_ok(n, f.data.shape[1], h, w) == 1)
+    """Is the data gradient of this layer the last layer's, served on the bf16 matrix pipe (ap_conv_final_dgrad_bf16)?
+    g, f: the gradient and the layer's input, as Feats or their forms."""
+    n, m, h, w = g.shape
+    return (K7_WGRAD and _plain_bf16_layer(spec, K7_EDGE) and m == 1 and not g.virtual and g.act == ACT_NONE and
+            g.dtype == torch.float32 and tuple(f.shape[2:]) == (h, w) and
+            C.lib().ap_conv_final_dgrad_bf16_ok(n, f.shape[1], h, w) == 1)
 
 
 def final_dgrad_k7(g, weight):
@@ -1247,13 +1312,12 @@ def final_dgrad_k7(g, weight):
 
 
 def head_dgrad_ok(spec, g, f):
-    """Is the data gradient of this layer the PatchGAN output layer's, served on the bf16 matrix pipe (ap_conv_head_dgrad_bf16)?"""
-    n, m, gh, gw = g.data.shape
-    h, w = f.data.shape[2:]
-    return (D0_MFMA and DEFAULT_PRECISION == PRECISION_BF16 and spec.precision == PRECISION_BF16 and not spec.transposed and
-            spec.k == 4 and spec.stride == 1 and spec.pad == 1 and spec.pad_mode == PAD_ZERO and m == 1 and not g.virtual and
-            g.act == ACT_NONE and g.data.dtype == torch.float32 and (gh, gw) == (h - 1, w - 1) and
-            C.lib().ap_conv_head_dgrad_bf16_ok(n, f.data.shape[1], h, w) == 1)
+    """Is the data gradient of this layer the PatchGAN output layer's, served on the bf16 matrix pipe (ap_conv_head_dgrad_bf16)?
+    g, f: the gradient and the layer's input, as Feats or their forms."""
+    n, m, gh, gw = g.shape
+    h, w = f.shape[2:]
+    return (D0_MFMA and _plain_bf16_layer(spec, HEAD_EDGE) and m == 1 and not g.virtual and g.act == ACT_NONE and
+            g.dtype == torch.float32 and (gh, gw) == (h - 1, w - 1) and C.lib().ap_conv_head_dgrad_bf16_ok(n, f.shape[1], h, w) == 1)
 
 
 def head_dgrad(g, weight, h, w):
@@ -1269,18 +1333,8 @@ def head_dgrad(g, weight, h, w):
     return gx
 
 
-def k7_stem_wgrad_ok(spec, g_shape, srcs):
-    """Does wgrad() serve this layer's weight gradient in the stem form of ap_wgrad_k7_bf16 (which also reads a bf16-stored gradient)?"""
-    n, m, h, w = g_shape
-    f = srcs[0]
-    return (K7_WGRAD and DEFAULT_PRECISION == PRECISION_BF16 and spec.precision == PRECISION_BF16 and not spec.transposed and
-            spec.k == 7 and spec.stride == 1 and spec.pad == 3 and spec.pad_mode == PAD_REFLECT and len(srcs) == 1 and
-            not f.virtual and f.act == ACT_NONE and f.data.dtype == torch.float32 and tuple(f.data.shape[2:]) == (h, w) and
-            not (m == 1 and f.data.shape[1] >= 32) and C.lib().ap_wgrad_k7_bf16_ok(n, m, f.data.shape[1], h, w, 0) == 1)
-
-
 def instnorm_bwd_split_ok(f, pad):
-    n, c, h, w = f.data.shape
+    n, c, h, w = f.shape
     return C.lib().ap_instnorm_bwd_split_ok(c, h, w, pad) == 1
 
 

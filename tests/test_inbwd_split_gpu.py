@@ -104,8 +104,8 @@ def test_layer_backward_with_prepared_operands_vs_autograd(dev, case):
             fx = tape.track(ops.Feat(x.to(dev)))
             out = autograd.conv_forward(tape, layer, [fx], norm_act=ops.ACT_NONE)
             gy = torch.randn(out.data.shape, generator=torch.Generator().manual_seed(5))
-            plan = autograd._split_backward_plan(tape, layer, [fx], out, [(gy.to(dev), 0)])
-            assert (plan is not None) == (off == '0'), (name, off)
+            plan = autograd._backward_plan(tape, layer, [fx], out, True, ops.ACT_NONE, [(gy.to(dev), 0)])
+            assert (plan.norm_route == 'split') == (off == '0'), (name, off)
             tape.add(out, gy.to(dev), 0)
             tape.backward()
             g1, p, g2 = ops._split_contribs(tape.take(fx))
