@@ -62,7 +62,7 @@ class ApWgradDesc(ctypes.Structure):
 
 
 # name -> (restype, argtypes); every symbol include/animateportrait_amd.h declares
-ABI_VERSION = 13     # AP_ABI_VERSION of include/animateportrait_amd.h this binding was written against
+ABI_VERSION = 14     # AP_ABI_VERSION of include/animateportrait_amd.h this binding was written against
 
 SIGNATURES = {
     'ap_abi_version': (ctypes.c_int32, []),
@@ -182,8 +182,8 @@ SIGNATURES = {
                                     ctypes.c_void_p]),
     'ap_tps_warp': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                    ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p, ctypes.c_void_p]),
-    'ap_adam_step': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
-                                    ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]),
+    'ap_adam_step': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p]),
     'ap_reduce_workspace_floats': (ctypes.c_int64, []),
     'ap_reduce_mean': (ctypes.c_int, [ctypes.c_int32, c_f32p, c_f32p, ctypes.c_float, ctypes.c_int64, ctypes.c_float,
                                       c_f32p, c_f32p, ctypes.c_void_p]),

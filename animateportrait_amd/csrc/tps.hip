@@ -13,7 +13,13 @@
 
 namespace apamd {
 
-constexpr int kTpsMaxN = 125;   // control points (+3 <= 128)
+// tps_solve_kernel keeps its augmented (n+3) x (n+5) system and the n control points in the 64 KiB of LDS a workgroup may ask
+// for: n = 123 needs 65 496 bytes, n = 124 would need 66 524.  kTpsMaxN is that limit, for the solve and the warp alike.
+constexpr size_t kTpsLdsLimit = 64 * 1024;
+constexpr size_t tps_solve_lds_bytes(int n) { return ((size_t)(n + 3) * (n + 5) + 2 * (size_t)n) * sizeof(float); }
+constexpr int kTpsMaxN = 123;   // control points
+static_assert(tps_solve_lds_bytes(kTpsMaxN) <= kTpsLdsLimit && tps_solve_lds_bytes(kTpsMaxN + 1) > kTpsLdsLimit,
+              "kTpsMaxN is the largest system that fits LDS");
 
 __device__ __forceinline__ float phi2(float r) { return 0.5f * r * logf(fmaxf(r, 1e-10f)); }
 
@@ -148,18 +154,19 @@ __global__ __launch_bounds__(256) void tps_warp_kernel(const float* __restrict__
     }
 }
 
-// fused Adam (torch.optim.Adam semantics, no weight decay / amsgrad): geomgm_ifw_fore_model.py:346-360
+// fused Adam (torch.optim.Adam semantics, no weight decay / amsgrad): geomgm_ifw_fore_model.py:346-360.  The host forms 1 - beta,
+// the bias corrections and lr / bc1 in double, as torch does, and hands them over rounded once (1.f - 0.999f is 1.3e-5 off 0.001).
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long long n, float lr, float b1, float b2, float eps, float bc1,
-                            float bc2_sqrt) {
+                            float* __restrict__ v, long long n, float step_size, float b1, float omb1, float b2, float omb2,
+                            float eps, float bc2_sqrt) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float gi = g[i];
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        const float mi = b1 * m[i] + omb1 * gi;
+        const float vi = b2 * v[i] + omb2 * gi * gi;
         m[i] = mi;
         v[i] = vi;
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] -= (lr / bc1) * (mi / denom);
+        p[i] -= step_size * (mi / denom);
     }
 }
 
@@ -172,10 +179,9 @@ extern "C" {
 int ap_tps_solve(const float* src, const float* dst, int32_t B, int32_t n, float* coef, int32_t* status,
                  ap_stream_t stream) {
     if (!src || !dst || !coef) return fail(AP_ERR_INVALID, "tps_solve: null pointer");
-    if (B < 1 || n < 3 || n > kTpsMaxN) return fail(AP_ERR_UNSUPPORTED, "tps_solve: n=%d (3..%d)", n, kTpsMaxN);
-    const int m = n + 3;
-    const size_t lds = ((size_t)m * (m + 2) + 2 * n) * sizeof(float);
-    if (lds > 64 * 1024) return fail(AP_ERR_UNSUPPORTED, "tps_solve: system of %d unknowns does not fit LDS", m);
+    if (B < 1 || n < 3 || n > kTpsMaxN)
+        return fail(AP_ERR_UNSUPPORTED, "tps_solve: B=%d n=%d (n in 3..%d: the system of n+3 unknowns is solved in LDS)", B, n, kTpsMaxN);
+    const size_t lds = tps_solve_lds_bytes(n);
     hipLaunchKernelGGL(tps_solve_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, src, dst, n, coef, status);
     return check_launch("tps_solve_kernel");
 }
@@ -190,14 +196,15 @@ int ap_tps_warp(const float* img, const float* dst, const float* coef, int32_t B
     return check_launch("tps_warp_kernel");
 }
 
-int ap_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                 float beta2, float eps, int32_t step, ap_stream_t stream) {
+int ap_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
+                 double beta2, double eps, int32_t step, ap_stream_t stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || n < 1 || step < 1) return fail(AP_ERR_INVALID, "adam_step: bad arguments");
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2 = 1.f - powf(beta2, (float)step);
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
     int blocks = (int)std::min<long long>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
-                       (long long)n, lr, beta1, beta2, eps, bc1, sqrtf(bc2));
+                       (long long)n, (float)(lr / bc1), (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                       (float)sqrt(bc2));
     return check_launch("adam_kernel");
 }
 

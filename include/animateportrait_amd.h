@@ -101,7 +101,7 @@ typedef struct ap_conv_desc {
  * ap_instnorm_finalize and gave ap_conv_desc.reserved a meaning as s2d_k without one).  A binding compares
  * ap_abi_version() with the AP_ABI_VERSION it was written against at load time and refuses a mismatch
  * (animateportrait_amd/_capi.py does). */
-#define AP_ABI_VERSION 13
+#define AP_ABI_VERSION 14
 int32_t ap_abi_version(void);
 const char* ap_version(void);
 const char* ap_last_error(void);
@@ -490,16 +490,18 @@ int ap_warp_concat_bwd(const float* gout, const float* motion, const float* flow
  * sparse_image_warp (Module2/models/sparse_image_warp.py:35-58): order-2 polyharmonic spline through n control
  * points (src -> dst, (row, col) order), dense flow, bilinear warp with edge clamping.  Batched (the reference is
  * b=1 only).  ap_tps_solve: coef = B x (n+3) x 2 (spline weights w then affine v); *status (optional device int) is
- * set to 1 if a system is singular (the reference drops into pdb there, :124-128).  ap_tps_warp: img / out are
+ * set to 1 if a system is singular (the reference drops into pdb there, :124-128).  n in 3..123 for both calls (the
+ * system of n+3 unknowns is solved in one workgroup's LDS); any other n is refused before a launch.  ap_tps_warp: img / out are
  * B x C x H x W (the reference passes NHWC; for its C=1 use both layouts coincide); flow_out (optional) B x H x W x 2. */
 int ap_tps_solve(const float* src, const float* dst, int32_t B, int32_t n, float* coef, int32_t* status,
                  ap_stream_t stream);
 int ap_tps_warp(const float* img, const float* dst, const float* coef, int32_t B, int32_t n, int32_t C, int32_t H,
                 int32_t W, float* out, float* flow_out, ap_stream_t stream);
 /* torch.optim.Adam(lr, betas=(beta1, beta2), eps) single step over a flat buffer
- * (Module2/models/geomgm_ifw_fore_model.py:346-360); step counts from 1. */
-int ap_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                 float beta2, float eps, int32_t step, ap_stream_t stream);
+ * (Module2/models/geomgm_ifw_fore_model.py:346-360); step counts from 1.  The hyper-parameters are doubles, as torch holds them:
+ * 1 - beta, the bias corrections and lr / (1 - beta1^step) are formed in double and rounded to fp32 once. */
+int ap_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
+                 double beta2, double eps, int32_t step, ap_stream_t stream);
 
 /* ======================================================================= losses, compositing, aux-net glue, rasterisers
  * (csrc/losses.hip).  Reductions are deterministic (fixed-order two-stage sums); `workspace` holds
