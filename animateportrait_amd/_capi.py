@@ -62,7 +62,7 @@ class ApWgradDesc(ctypes.Structure):
 
 
 # name -> (restype, argtypes); every symbol include/animateportrait_amd.h declares
-ABI_VERSION = 14     # AP_ABI_VERSION of include/animateportrait_amd.h this binding was written against
+ABI_VERSION = 15     # AP_ABI_VERSION of include/animateportrait_amd.h this binding was written against
 
 SIGNATURES = {
     'ap_abi_version': (ctypes.c_int32, []),
@@ -122,6 +122,9 @@ SIGNATURES = {
                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]),
     'ap_motion_grid': (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_int32, c_f32p, ctypes.c_void_p]),
+    'ap_delaunay': (ctypes.c_int, [c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p]),
+    'ap_delaunay_ok': (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     'ap_resize_bilinear': (ctypes.c_int, [c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_int32, c_f32p, ctypes.c_void_p]),
     'ap_grid_sample': (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -86,7 +86,7 @@ def landmarks_from_audio(a, device):
     return module1.photo_landmarks_in_pixels(face_id, scale, shift), seq.astype(np.float32)
 
 
-def main(argv=None):
+def make_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--photo', required=True)
     ap.add_argument('--landmarks', default=None, help='directory in the Alm_txt layout')
@@ -112,6 +112,14 @@ def main(argv=None):
     ap.add_argument('--max_frames', type=int, default=None)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--size', type=int, default=256)
+    ap.add_argument('--triangulate', choices=('host', 'device'), default='host',
+                    help='where the motion grids\' Delaunay triangulation runs: scipy on the CPU per frame, or ap_delaunay on the GPU '
+                         '(the landmark sequence is then uploaded once and no per-frame work is left on the host)')
+    return ap
+
+
+def main(argv=None):
+    ap = make_parser()
     a, rest = ap.parse_known_args(argv)
     if sum(x is not None for x in (a.landmarks, a.landmarks_npy, a.wav)) != 1:
         ap.error('exactly one of --landmarks / --landmarks_npy / --wav')
@@ -144,7 +152,7 @@ def main(argv=None):
     matte = load_matte(a.matte, a.size) if a.matte else None
     if matte is None and model.aux.get('modnet') is None:
         raise SystemExit('no matting network is attached (aux["modnet"]): pass --matte PNG')
-    frames = stream.ClipStreamer(model, batch=a.batch).run(photo, lm0, seq, matte=matte)
+    frames = stream.ClipStreamer(model, batch=a.batch, triangulate=a.triangulate).run(photo, lm0, seq, matte=matte)
     fdir = os.path.join(a.out, 'frames')
     os.makedirs(fdir, exist_ok=True)
     from PIL import Image

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import losses, ops
-from .data.motion import cal_motion256
+from .data.motion import cal_motion256, check_triangulations
 
 
 def read_landmark_txt(path):
@@ -81,10 +81,14 @@ def window_of(lm, size=256, margin=0.15):
 
 
 class ClipStreamer:
-    """Drives a ``GeomCGTIFWTestModel`` over a landmark sequence in batches of ``batch`` frames."""
+    """Drives a ``GeomCGTIFWTestModel`` over a landmark sequence in batches of ``batch`` frames.
+    triangulate: 'host' -- the motion grids' Delaunay triangulation runs per frame on the CPU (scipy); 'device' -- on the GPU
+    (``ap_delaunay``): the landmark sequence is uploaded once and sliced there, and no stage of the loop touches the host."""
 
-    def __init__(self, model, batch=16):
-        self.model, self.batch = model, int(batch)
+    def __init__(self, model, batch=16, triangulate='host'):
+        if triangulate not in ('host', 'device'):
+            raise ValueError("ClipStreamer: triangulate must be 'host' or 'device', not %r" % (triangulate,))
+        self.model, self.batch, self.triangulate = model, int(batch), triangulate
         self.device = model.device
         self.timing = {}
 
@@ -107,6 +111,9 @@ class ClipStreamer:
         out = torch.empty((t_total, m.opt.output_nc, s, s), dtype=torch.float32, device=dev)
         self.timing = {}
         photo_b, alm_b, matte_b = {}, {}, {}
+        on_device = self.triangulate == 'device'
+        if on_device:                                # the clip's landmarks cross to the device once
+            lm0_dev, seq_dev = lm0.to(dev), seq.to(dev)
         ClipStreamer._clips = getattr(ClipStreamer, '_clips', 0) + 1
         clip_id = ('clip', ClipStreamer._clips)      # names this run's constant photo landmark map for the generator's cache
         for lo in range(0, t_total, self.batch):
@@ -118,11 +125,14 @@ class ClipStreamer:
                 matte_b[b] = None if matte is None else matte.to(dev).float().expand(b, -1, -1, -1).contiguous()
             lm_t = seq[lo:hi]
             t0 = time.perf_counter()
-            motion = cal_motion256(lm0.unsqueeze(0).expand(b, -1, -1).numpy(), lm_t.numpy(), device=dev, size=s)
+            if on_device:
+                motion = cal_motion256(lm0_dev.unsqueeze(0).expand(b, -1, -1), seq_dev[lo:hi], device=dev, size=s, triangulate='device')
+            else:
+                motion = cal_motion256(lm0.unsqueeze(0).expand(b, -1, -1).numpy(), lm_t.numpy(), device=dev, size=s)
             if profile:
                 self._tick('motion_grid', t0)
             t0 = time.perf_counter()
-            lm_dev = lm_t.to(dev)
+            lm_dev = seq_dev[lo:hi] if on_device else lm_t.to(dev)
             tb_lm = losses.landmark_discs(lm_dev, s, s, 5 if s == 512 else 3)
             if profile:
                 self._tick('landmark_maps', t0)
@@ -145,6 +155,8 @@ class ClipStreamer:
                 self._tick('generator', t0)
         if ops.FUSED_NORM:
             ops.check_fused_norm()                   # opt-in in-kernel InstanceNorm: a timed-out exchange invalidates the clip
+        if on_device:
+            check_triangulations(dev)                # more triangles than rows in some frame: its grid is invalid
         return out
 
 

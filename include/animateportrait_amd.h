@@ -101,7 +101,7 @@ typedef struct ap_conv_desc {
  * ap_instnorm_finalize and gave ap_conv_desc.reserved a meaning as s2d_k without one).  A binding compares
  * ap_abi_version() with the AP_ABI_VERSION it was written against at load time and refuses a mismatch
  * (animateportrait_amd/_capi.py does). */
-#define AP_ABI_VERSION 14
+#define AP_ABI_VERSION 15
 int32_t ap_abi_version(void);
 const char* ap_version(void);
 const char* ap_last_error(void);
@@ -299,6 +299,26 @@ int ap_warp_concat_fwd(const float* x, const float* x_mean, const float* x_rstd,
  * coordinates ((col, row) / ((S-1)/2) - 1), i.e. the `warp_motion` input of the generator. */
 int ap_motion_grid(const float* pts, const float* val, const int32_t* tri, int32_t N, int32_t P, int32_t T, int32_t S,
                    float* out, ap_stream_t stream);
+/* Delaunay triangulation of N independent planar point sets on the device (ABI 15): the triangulation half of
+ * cal_motion256 (scipy.spatial.Delaunay inside griddata), so that the landmarks never visit the host.
+ *   pts:   [N][P][2] float32, the layout ap_motion_grid reads (row, col)
+ *   tri:   [N][Tcap][3] int32 out; rows past count[n] are written -1, so tri feeds ap_motion_grid with T = Tcap
+ *   count: [N] int32 out; number of triangles, or -1 if more than Tcap were found (then all rows of that set are -1)
+ * Served region (ap_delaunay_ok(N, P, Tcap) == 1, no launch): 1 <= N <= 65535, 3 <= P <= 128, 1 <= Tcap and
+ * Tcap * 12 * 4 bytes <= 60 KiB (the LDS table of ap_motion_grid).  Outside it, or for a null pointer, an error code is
+ * returned and nothing is launched.
+ * Contract (the result is unique):
+ *   - a point whose coordinates are bit-equal to an EARLIER point of its set is dead and appears in no triangle;
+ *   - predicates (orientation; in-circle as the 3x3 determinant relative to the query point) are evaluated in fp64 on
+ *     coordinate differences -- exact for integer coordinates with |x| <= 1024;
+ *   - a triple a < b < c of live points is emitted iff (i) it is not collinear, (ii) no live point lies strictly inside
+ *     its circumcircle, (iii) if live points lie exactly ON the circle, the lowest index among them and a, b, c is one
+ *     of a, b, c (v0), and (iv) every such on-circle point lies strictly on v0's side of the line through the other two
+ *     vertices: a cocircular polygon is fanned from its lowest-index vertex, so the output is a proper tiling;
+ *   - rows hold ascending vertex indices and come in ascending lexicographic order: the same input gives the same bits;
+ *   - fewer than 3 live points, or all live points collinear: count = 0. */
+int ap_delaunay(const float* pts, int32_t N, int32_t P, int32_t Tcap, int32_t* tri, int32_t* count, ap_stream_t stream);
+int ap_delaunay_ok(int32_t N, int32_t P, int32_t Tcap);
 /* Image-level helpers of the streaming-inference model (geomcgt_ifw_test_model.py:282-285, 294):
  * y = F.interpolate(x, (OH, OW), mode='bilinear', align_corners=False) over NC planes, and
  * y = F.grid_sample(x, grid, mode='bilinear', padding_mode='zeros', align_corners=...) with grid (N, OH, OW, 2). */
