@@ -45,7 +45,6 @@ void bf3_register_row_half(std::vector<Bf3Kernel>&);     // ... 32 couts x 8 row
 void bf3_register_taps12(std::vector<Bf3Kernel>&);       // run-time taps: 1 and 2 taps (sub-pixel phases)
 void bf3_register_taps4(std::vector<Bf3Kernel>&);        // run-time taps: 4 taps, full height
 void bf3_register_taps4_half(std::vector<Bf3Kernel>&);   // ... half height (two per CU) + its space-to-depth 3x3 tap sets
-const void* bf3_fnorm_kernel();                          // Bf3Cfg<1,3,1,2,4,4,...,FNORM>: convolution + InstanceNorm in one launch
 const Bf3Kernel* ph4_kernel(int KK);                     // conv_ph4.h: 3 or 4
 
 }  // namespace apamd

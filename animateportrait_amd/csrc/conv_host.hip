@@ -778,43 +778,6 @@ static bool ob16_plan_ok(const ap_conv_desc* d, const Plan& pl) {
     return pl.bk && pl.bk->fn1_ob16 != nullptr;
 }
 
-// ---- convolution + InstanceNorm in one launch (conv_bf16x3<..., FNORM>): which plans qualify, and is the launch deadlock-free?
-// The workgroups holding the tiles of one (image, cout tile) wait for each other inside the kernel, so they must all be running
-// at the same time: the persistent grid puts at most one workgroup on a CU and walks the tile list in rounds (workgroup b of an XCD
-// takes tiles base + idx, base + idx + step, ...); every group has to lie inside ONE round of ONE XCD's range.
-static bool fnorm_plan_ok(const ap_conv_desc* d, const Plan& pl) {
-    if (!pl.bf3 || pl.fused_phases || pl.ph4 || pl.launches.size() != 1 || d->transposed || d->precision != AP_PRECISION_BF16X3 ||
-        env_int("APAMD_NO_FUSED_NORM", 0))
-        return false;
-    const Bf3Kernel* k = pl.bk;
-    if (!k || k->S != 1 || k->K != 3 || k->ROW || k->TH != 16 || k->CO_TILE != 64) return false;
-    if ((d->Cout % 64) || (pl.Hout % 16) || (pl.Wout % 32)) return false;           // whole tiles only: every lane holds real pixels
-    if ((pl.Hout / 16) * (pl.Wout / 32) > 32) return false;                          // the exchange table holds 32 tiles per plane
-    const Launch& L = pl.launches[0];
-    const long long per_image = (long long)L.tiles_y * L.tiles_x * pl.co_tiles, ntl = d->N * per_image;
-    const long long G = ntl < num_cus() ? ntl : num_cus();
-    const long long nx = G < 8 ? G : 8, q = ntl / nx, r = ntl % nx;
-    for (int n = 0; n < d->N; ++n) {
-        // the tiles of image n are contiguous in the list ((n, ty, tx) major, cout tile fastest): all of them in one round
-        const long long t0 = n * per_image, t1 = t0 + per_image - 1;
-        auto where = [&](long long t, long long& xcd, long long& round) {
-            for (xcd = 0; xcd < nx; ++xcd) {
-                const long long base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, cnt = q + (xcd < r ? 1 : 0);
-                if (t >= base && t < base + cnt) {
-                    const long long step = (G - xcd + nx - 1) / nx;
-                    round = (t - base) / step;
-                    return;
-                }
-            }
-        };
-        long long x0 = -1, r0 = -1, x1 = -2, r1 = -2;
-        where(t0, x0, r0);
-        where(t1, x1, r1);
-        if (x0 != x1 || r0 != r1) return false;
-    }
-    return true;
-}
-
 // the answer of an ap_conv2d_*_ok query: the descriptor has a plan and the plan passes the predicate
 static int32_t plan_passes(const ap_conv_desc* d, bool (*ok)(const ap_conv_desc*, const Plan&)) {
     Plan pl;
@@ -827,7 +790,6 @@ struct OutForm {
     const ap_out_view* view = nullptr;   // a window of the output, with the caller's strides
     bool octet = false;                  // channel-octet layout y[n][Cout/8][OH*OW][8]
     bool bf16 = false;                   // bf16 values
-    const ap_fused_norm* fn = nullptr;   // InstanceNorm of the output inside the epilogue (y is then the exchange buffer)
 };
 
 struct FwdArgs {
@@ -838,10 +800,8 @@ struct FwdArgs {
 
 // Every refusal that depends on the arguments, before anything is launched; callers tell the refusals apart, so the order stays
 static int check_fwd_args(const ap_conv_desc* d, const Plan& pl, const OutForm& o, const FwdArgs& a) {
-    if (o.bf16 && (!ob16_plan_ok(d, pl) || o.octet || o.fn))
+    if (o.bf16 && (!ob16_plan_ok(d, pl) || o.octet))
         return fail(AP_ERR_UNSUPPORTED, "conv2d_fwd_bf16out: only the plain-bf16 dense 3x3 stride-1 layers store bf16 (ap_conv2d_bf16out_ok)");
-    if (o.fn && !fnorm_plan_ok(d, pl))
-        return fail(AP_ERR_UNSUPPORTED, "conv2d_fwd_norm: this layer / shape cannot normalise in its epilogue (ap_conv2d_fused_norm_ok)");
     if (!a.packed || !a.y) return fail(AP_ERR_INVALID, "null packed/y pointer");
     if (o.octet && !octet_plan_ok(d, pl))
         return fail(AP_ERR_UNSUPPORTED, "conv2d_fwd_octet: only single-launch split-bf16 layers of the run-time-tap / row kernel "
@@ -1089,26 +1049,19 @@ static int launch_bf3(const ap_conv_desc* d, const Plan& pl, const OutForm& o, c
         // even chunk count per input phase: the instantiation with compile-time tap sets (no fragment reads for absent taps)
         if (p.s2d_div > 0 && (p.s2d_div & 1) == 0 && p.nchunks == 4 * p.s2d_div && kern->kernel_s2d3(d->precision))
             kfn = kern->kernel_s2d3(d->precision);
-        if (const ap_fused_norm* fn = o.fn) {
-            kfn = bf3_fnorm_kernel();
-            p.fn_act = fn->act; p.fn_eps = fn->eps; p.fn_inv_count = 1.0 / ((double)pl.Hout * pl.Wout);
-            p.fn_res_oct = fn->res_oct; p.fn_res_nchw = fn->res_nchw; p.fn_y_oct = fn->y_oct; p.fn_xs = fn->xs;
-            p.fn_mean = fn->mean; p.fn_rstd = fn->rstd; p.fn_counters = fn->counters;
-            p.fn_debug = env_int("APAMD_FNORM_DEBUG", 0);
-        }
         rc = ensure_dyn_lds(kfn, 160 * 1024);
         if (rc) return rc;
         size_t lds = kern->lds(d->precision, p.ntaps);
         bool sb = false;
 #ifdef APAMD_VARIANTS
-        if (!o.fn && !o.view && !o.octet && kern->K == 3 && kern->S == 1 && kern->TH == 16 && !kern->ROW && d->precision != AP_PRECISION_BF16 &&
+        if (!o.view && !o.octet && kern->K == 3 && kern->S == 1 && kern->TH == 16 && !kern->ROW && d->precision != AP_PRECISION_BF16 &&
             p.osx == 1 && p.osy == 1 && p.oy_off == 0 && p.ox_off == 0 && env_int("APAMD_CONV_SB", 0)) {
             // rejected experiment kept for A/B (tools/variants/conv_bf16x3_sb.h, `make variants`): one LDS stage per
             // workgroup, two workgroups per CU
             kfn = bf3_sb_kernel(&lds);
             rc = ensure_dyn_lds(kfn, 160 * 1024);
             if (rc) return rc;
-            p.fn_debug = env_int("APAMD_CONV_SB_SKEW", 0);
+            p.sb_skew = env_int("APAMD_CONV_SB_SKEW", 0);
             sb = true;
         }
 #endif
@@ -1160,13 +1113,6 @@ extern "C" {
 
 int32_t ap_conv2d_octet_ok(const ap_conv_desc* d) { return plan_passes(d, octet_plan_ok); }
 int32_t ap_conv2d_bf16out_ok(const ap_conv_desc* d) { return plan_passes(d, ob16_plan_ok); }
-int32_t ap_conv2d_fused_norm_ok(const ap_conv_desc* d) { return plan_passes(d, fnorm_plan_ok); }
-
-int32_t ap_conv2d_fused_norm_counters(const ap_conv_desc* d) {
-    Plan pl;
-    int rc = make_plan(d, pl);
-    return rc ? rc : d->N * pl.co_tiles * 2 + 1;        // + the launch's error flag (set when a workgroup gave up waiting)
-}
 
 int ap_conv2d_fwd(const ap_conv_desc* d, const float* packed, const float* bias, float* y,
                   float* stat_partials, ap_stream_t stream) {
@@ -1202,16 +1148,6 @@ int ap_conv2d_fwd_view_bf16out(const ap_conv_desc* d, const ap_out_view* view, c
     o.view = view;
     o.bf16 = true;
     return conv2d_fwd_impl(d, o, {packed, bias, reinterpret_cast<float*>(y_bf16), nullptr, (hipStream_t)stream});
-}
-
-int ap_conv2d_fwd_norm(const ap_conv_desc* d, const float* packed, const ap_fused_norm* fn, ap_stream_t stream) {
-    if (!fn || !fn->partials || !fn->counters || !fn->mean || !fn->rstd) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: null workspace");
-    if (!fn->xs && !fn->y_oct) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: neither a split nor a channel-octet output");
-    if (fn->res_oct && fn->res_nchw) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: two residuals");
-    if (fn->act < 0 || fn->act > 2) return fail(AP_ERR_INVALID, "conv2d_fwd_norm: act %d", fn->act);
-    OutForm o;
-    o.fn = fn;
-    return conv2d_fwd_impl(d, o, {packed, nullptr, fn->partials, fn->partials, (hipStream_t)stream});
 }
 
 }  // extern "C"

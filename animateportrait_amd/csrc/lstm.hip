@@ -16,8 +16,8 @@
 //     W_hh in registers for the whole sequence (W_hh is read from memory ONCE), h_{t-1} is exchanged through a 2 x H global
 //     buffer and a monotonic arrival counter per step.  All accesses to the exchange data are agent-scope relaxed atomics
 //     (performed at the coherence point: the per-CU L1 is never refreshed by another CU's stores), ordered by waiting for the
-//     stores' acknowledgement before the workgroup barrier that precedes the counter bump (the protocol of conv_bf16x3.h's
-//     in-kernel InstanceNorm).  The workers are the blocks b with b % 8 == 0 of an 8 x larger grid -- one XCD.
+//     stores' acknowledgement before the workgroup barrier that precedes the counter bump.  The workers are the blocks b with
+//     b % 8 == 0 of an 8 x larger grid -- one XCD.
 #include "common.h"
 
 #include <cstdint>

@@ -99,18 +99,6 @@ class ConvLayer(nn.Module):
             return False
         return ops.takes_split(self.spec, n, h, w)
 
-    def fused_norm_ok(self, srcs):
-        """Inference only: can this layer produce act(IN(conv)) [+ residual] in one launch (ops.conv2d_norm)?"""
-        if not isinstance(srcs, (list, tuple)):
-            srcs = [srcs]
-        return (not ops.stem_rows_eligible(self.spec) and not ops.s2d_eligible(self.spec, *srcs[0].data.shape[2:])
-                and ops.fused_norm_ok(self.spec, srcs))
-
-    def run_norm(self, srcs, act=ACT_NONE, residual=None, want_oct=False, want_xs=True):
-        if not isinstance(srcs, (list, tuple)):
-            srcs = [srcs]
-        return ops.conv2d_norm(self.spec, srcs, self.packed(), act=act, residual=residual, want_oct=want_oct, want_xs=want_xs)
-
     def s2d_spec(self):
         if self._s2d_spec is None:
             self._s2d_spec = ops.s2d_spec(self.spec)
@@ -145,11 +133,6 @@ class ResnetBlock(nn.Module):
         """consumer: the layer that reads the block's output when it is not another block of the trunk (the first
         up-convolution) -- the output is kept as fp32 unless that layer stages split copies."""
         c1, c5 = self.conv_block['1'], self.conv_block['5']
-        if tape is None and not x.virtual and (x.oct is not None or not x.is_split_only) and c1.fused_norm_ok(x):
-            # inference: each convolution normalises its own output in the epilogue (ap_conv2d_fwd_norm) -- no raw fp32 output,
-            # no norm_split pass; the block's result lives as the split copy (next convolution) + channel-octet fp32 (next residual)
-            y = c1.run_norm(x, act=ACT_RELU)
-            return c5.run_norm(y, act=ACT_NONE, residual=x, want_oct=True)
         # (raw16: c1's raw output is read by c5's split pass, its own InstanceNorm backward and c5's weight gradient; c5's by the
         # residual pass and its InstanceNorm backward -- all of which read bf16: plain-bf16 training stores them as bf16)
         # inference: the raw outputs leave in the channel-octet layout where their one reader is a split-only norm pass (ops.trunk_octet_ok)
@@ -172,11 +155,6 @@ class ResnetBlock2(nn.Module):
 
     def run(self, srcs, tape=None, consumer=None):
         c1, c5, sc = self.conv_block['1'], self.conv_block['5'], self.shortcut['0']
-        if tape is None and c1.fused_norm_ok(srcs):
-            # inference (see ResnetBlock.run): the shortcut's IN(conv) is the residual of the main branch's second convolution
-            s = sc.run_norm(srcs, act=ACT_NONE, want_oct=True, want_xs=False)
-            y = c1.run_norm(srcs, act=ACT_RELU)
-            return c5.run_norm(y, act=ACT_NONE, residual=s, want_oct=True)
         y = conv_forward(tape, c1, srcs, norm_act=ACT_RELU, raw16=True, out_octet=tape is None and ops.trunk_octet_ok(c1.spec.cout))
         y = conv_forward(tape, c5, y, norm_act=ACT_NONE, raw16=True)
         s = conv_forward(tape, sc, srcs, norm_act=ACT_NONE)            # (the shortcut's raw output is read as a normalised RESIDUAL: fp32)

@@ -571,7 +571,7 @@ def trunk_octet_ok(c, residual=None, keep_fp32=False):
     """Inference: may a trunk convolution whose raw output is read by ONE ap_norm_apply_split pass -- split copy out, residual none
     or the previous block's split copy -- write the channel-octet layout (no LDS transposition in its epilogue, no LDS staging in
     the pass)?  Mirrors the conditions under which materialize() keeps only the split copy."""
-    if (DEFAULT_PRECISION != PRECISION_BF16X3 or FUSED_NORM or not RESIDUAL_AS_SPLIT or not OCTET_TRUNK or keep_fp32 or
+    if (DEFAULT_PRECISION != PRECISION_BF16X3 or not RESIDUAL_AS_SPLIT or not OCTET_TRUNK or keep_fp32 or
             not wants_split(c) or c % 8):
         return False
     return residual is None or (residual.is_split_only and residual.xs is not None and not residual.xs_heads_only and residual.oct is None)
@@ -661,30 +661,6 @@ def conv2d(spec, srcs, packed, bias=None, act=ACT_NONE, want_stats=False, out_ac
     return Feat(y, act=out_act, pending=(partial, tiles))
 
 
-_FNORM_FLAGS = []          # counter buffers of recent ap_conv2d_fwd_norm launches (their last element is the kernel's error flag)
-
-
-_COUNTER_POOL = {}         # device -> [zero-initialised int32 pool, next free offset]
-
-
-def _zero_counters(n, device):
-    """n zero int32 counters for one ap_conv2d_fwd_norm launch, cut from a pool that is zeroed once (a torch.zeros per launch was
-    a 5 us fill kernel in front of each of the 21 trunk convolutions).  A slice is used by exactly one launch."""
-    pool = _COUNTER_POOL.get(device)
-    if pool is None or pool[1] + n > pool[0].numel():
-        pool = _COUNTER_POOL[device] = [torch.zeros(1 << 20, dtype=torch.int32, device=device), 0]
-    out = pool[0][pool[1]:pool[1] + n]
-    pool[1] += (n + 3) & ~3
-    return out
-
-
-# Convolution + InstanceNorm in one launch (ap_conv2d_fwd_norm) for the trunk of the generators in inference: OPT-IN.  Measured at
-# B = 16 it removes the 18 norm_split passes of a forward (0.6 ms) and gives the time back in its own epilogue -- every workgroup
-# bursts its (larger) output at the same moment and the matrix pipe idles meanwhile: 2131 vs 2110 and 2207 vs 2204 frames/s on two
-# boxes (DESIGN.md section 3.10, HISTORY.md section 3.11).  Not worth a kernel that waits on its peers by default.
-FUSED_NORM = os.environ.get('APAMD_FUSED_NORM', '0') == '1'
-
-
 # Inference: the ResNet trunk's residual stream is kept only as split copies (materialize keep_fp32=False; HISTORY.md section 3.10).
 # (tests flip the flag to compare with the fp32 stream)
 RESIDUAL_AS_SPLIT = True
@@ -692,79 +668,6 @@ RESIDUAL_AS_SPLIT = True
 K7_WGRAD = os.environ.get('APAMD_NO_K7_WGRAD', '0') != '1'
 # ... and the PatchGAN's first layer as an output stream on the matrix pipe (conv_d0.h); 0: the fp32 implicit-GEMM kernel (A/B)
 D0_MFMA = K7_WGRAD and os.environ.get('APAMD_NO_D0_MFMA', '0') != '1'
-
-
-def fused_norm_ok(spec, srcs):
-    """Can this layer, at this shape, normalise its own output in the epilogue (ap_conv2d_fwd_norm), and is that form switched on?"""
-    if not FUSED_NORM or spec.precision != PRECISION_BF16X3 or DEFAULT_PRECISION != PRECISION_BF16X3:
-        return False
-    n, _, h, w = srcs[0].data.shape
-    d = spec.presplit_desc(n, h, w)
-    return C.lib().ap_conv2d_fused_norm_ok(ctypes.byref(d)) == 1
-
-
-def conv2d_norm(spec, srcs, packed, act=ACT_NONE, residual=None, want_oct=False, want_xs=True):
-    """``act(InstanceNorm(conv(srcs))) [+ residual]`` in ONE launch (inference: nothing is kept for a backward pass).
-    residual: a materialised Feat -- its channel-octet fp32 copy (``.oct``) when it has one, else its NCHW tensor.
-    Returns a materialised Feat that exists as its split-bf16 copy (``.xs``, want_xs) and / or as channel-octet fp32 (``.oct``,
-    want_oct: what the next block's residual add reads); its NCHW tensor is never written."""
-    x0 = srcs[0].data
-    n, _, h, w = x0.shape
-    d = spec.presplit_desc(n, h, w, srcs)
-    lib = C.lib()
-    ho, wo = ctypes.c_int32(), ctypes.c_int32()
-    C.check(lib.ap_conv2d_out_size(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), 'conv2d_out_size')
-    dev, cout, hw = x0.device, spec.cout, ho.value * wo.value
-    tiles = C.check(lib.ap_conv2d_stat_tiles(ctypes.byref(d)), 'conv2d_stat_tiles')
-    nctr = C.check(lib.ap_conv2d_fused_norm_counters(ctypes.byref(d)), 'fused_norm_counters')
-    fn = C.ApFusedNorm()
-    fn.act, fn.eps = act, EPS
-    partial = torch.empty((n * cout, tiles, 2), dtype=torch.float32, device=dev)
-    counters = _zero_counters(nctr, dev)
-    mean = torch.empty(n * cout, dtype=torch.float32, device=dev)
-    rstd = torch.empty_like(mean)
-    fn.partials, fn.counters, fn.mean, fn.rstd = partial.data_ptr(), counters.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-    if residual is not None:
-        if residual.virtual:
-            raise RuntimeError('conv2d_norm: the residual must be a materialised feature')
-        if residual.oct is not None:
-            fn.res_oct = residual.oct.data_ptr()
-        else:
-            if residual.is_split_only:
-                raise RuntimeError('conv2d_norm: the residual exists only as its split-bf16 copy')
-            _require_device(residual.data, 'residual')
-            fn.res_nchw = residual.data.data_ptr()
-    y_oct = xs = None
-    if want_oct:
-        y_oct = torch.empty((n, cout // 8, hw, 8), dtype=torch.float32, device=dev)
-        fn.y_oct = y_oct.data_ptr()
-    if want_xs:
-        xs = _alloc_xs((n, cout, ho.value, wo.value), dev)
-        fn.xs = xs.data_ptr()
-    if PROFILER is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    C.check(lib.ap_conv2d_fwd_norm(ctypes.byref(d), _ptr(packed), ctypes.byref(fn), _stream()), 'conv2d_fwd_norm')
-    if PROFILER is not None:
-        e1.record()
-        macs = sum(spec.cin_segments) * spec.k ** 2
-        PROFILER.records.append(('Bf3Cfg<1, 3, 1, 2, 4, 4> +IN', 2.0 * n * hw * cout * macs, e0, e1))
-    _FNORM_FLAGS.append(counters)
-    if len(_FNORM_FLAGS) > 256:
-        check_fused_norm()
-    res = Feat(_stand_in((n, cout, ho.value, wo.value), dev))
-    res.xs, res.oct = xs, y_oct
-    return res
-
-
-def check_fused_norm():
-    """Deferred check of the error flags of the ap_conv2d_fwd_norm launches since the last call (one device read): a set flag
-    means a workgroup gave up waiting for its group -- the device was shared with other work -- and the results are invalid."""
-    global _FNORM_FLAGS
-    flags, _FNORM_FLAGS = _FNORM_FLAGS, []
-    if flags and int(torch.stack([c[-1] for c in flags]).max()) != 0:
-        raise RuntimeError('animateportrait_amd: a convolution with in-kernel InstanceNorm timed out waiting for its peer workgroups '
-                           '(is the GPU shared with another process or stream?); set APAMD_NO_FUSED_NORM=1')
 
 
 def _conv2d_view(spec, srcs, packed, out, view):
@@ -825,8 +728,7 @@ def materialize(f, residual=None, emit_xs=None, keep_fp32=True):
     if emit_xs is None:
         emit_xs = wants_split(c)
     if c % 8 == 0:
-        # (with the opt-in in-kernel InstanceNorm the next block's fused epilogue reads its residual as fp32: keep it)
-        split_only = (bool(emit_xs) and not keep_fp32 and RESIDUAL_AS_SPLIT and not FUSED_NORM and
+        split_only = (bool(emit_xs) and not keep_fp32 and RESIDUAL_AS_SPLIT and
                       DEFAULT_PRECISION == PRECISION_BF16X3)
         if residual is not None and residual.is_split_only and not split_only and residual.xs_heads_only:
             raise RuntimeError('materialize: the residual exists only as a head-only split copy')

@@ -153,8 +153,6 @@ class ClipStreamer:
             out[lo:hi] = m.fake_B
             if profile:
                 self._tick('generator', t0)
-        if ops.FUSED_NORM:
-            ops.check_fused_norm()                   # opt-in in-kernel InstanceNorm: a timed-out exchange invalidates the clip
         if on_device:
             check_triangulations(dev)                # more triangles than rows in some frame: its grid is invalid
         return out

@@ -20,7 +20,7 @@ ZERO, REFLECT = 0, 1
 OIHW, IOHW = 0, 1
 # every environment switch make_plan and the *_ok predicates read
 PLAN_ENV = ('APAMD_NO_SMALL', 'APAMD_NO_BF16X3', 'APAMD_NO_SMALL_TILES', 'APAMD_CONV_COTILE', 'APAMD_CONV_LDS_TARGET',
-            'APAMD_CONV_CI', 'APAMD_NO_FUSED_NORM')
+            'APAMD_CONV_CI')
 CONFIGS = {'default': {}, 'no_small_tiles': {'APAMD_NO_SMALL_TILES': '1'}, 'no_bf16x3': {'APAMD_NO_BF16X3': '1'}}
 CONFIG_ORDER = ('default', 'no_small_tiles', 'no_bf16x3')
 COUTS = (1, 2, 4, 8, 16, 32, 48, 64, 96, 128, 256, 512)
@@ -47,8 +47,7 @@ def sweep():
              (7, 5, 3), (40, 8), (64, 12), (9,)]
     add([_layer(s, 64, 3, 1, 1, ZERO) for s in segs3], [(2, 32, 32)], F_X3)
     add([_layer(s, 16, 3, 1, 1, REFLECT) for s in ((128,), (112,), (256, 16), (8,), (16,), (12,))], [(2, 64, 64)], F_X3)
-    # ... both sides of the tall / short tile rule (128 | 136 tiles of 16 rows; maps no taller than the short tile) and the
-    # whole-tile, one-round conditions of the fused InstanceNorm epilogue
+    # ... both sides of the tall / short tile rule (128 | 136 tiles of 16 rows; maps no taller than the short tile)
     add([_layer((64,), 64, 3, 1, 1, REFLECT), _layer((256,), 256, 3, 1, 1, REFLECT)],
         [(16, 64, 64), (17, 64, 64), (8, 64, 64), (40, 4, 66), (40, 5, 66), (64, 2, 64), (16, 60, 64), (16, 64, 48),
          (1, 256, 256), (1, 8, 37)], X3_16)
@@ -125,7 +124,7 @@ def _desc(prec, layer, shape):
 
 def answers(lib, prec, layer, shape):
     """What the planner says about one descriptor: [rc, Hout, Wout, packed floats, stat tiles, wants presplit, kernel name (or its
-    refusal code), octet ok, bf16out ok, fused norm ok, fused norm counters]."""
+    refusal code), octet ok, bf16out ok]."""
     d = _desc(prec, layer, shape)
     ref = ctypes.byref(d)
     ho, wo = ctypes.c_int32(-1), ctypes.c_int32(-1)
@@ -134,7 +133,7 @@ def answers(lib, prec, layer, shape):
     nrc = lib.ap_conv2d_kernel_name(ref, buf, 96)
     return [rc, ho.value, wo.value, lib.ap_conv2d_packed_floats(ref), lib.ap_conv2d_stat_tiles(ref),
             lib.ap_conv2d_wants_presplit(ref), buf.value.decode() if nrc == 0 else nrc, lib.ap_conv2d_octet_ok(ref),
-            lib.ap_conv2d_bf16out_ok(ref), lib.ap_conv2d_fused_norm_ok(ref), lib.ap_conv2d_fused_norm_counters(ref)]
+            lib.ap_conv2d_bf16out_ok(ref)]
 
 
 def _table(lib):
@@ -188,7 +187,7 @@ def test_the_sweep_reaches_every_family_and_refusal(golden):
         assert any(n.startswith(prefix) for n in names), prefix
     assert any(n.endswith(' bf16') for n in names)
     assert {a[0] for a in rows} == {0, -1, -2}
-    for col in (5, 7, 8, 9):                       # wants presplit, octet, bf16 out, fused norm: answered both ways
+    for col in (5, 7, 8):                          # wants presplit, octet, bf16 out: answered both ways
         assert {a[col] for a in rows if a[0] == 0} == {0, 1}, col
     # (the 1 x 7 row form exists on the split-bf16 path only and does not read the switch)
     assert all(a[5] == 0 for r, a in zip(golden, _recorded(golden, 'no_bf16x3')) if a[0] == 0 and r[1][2] == r[1][3])

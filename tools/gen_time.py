@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the B = 16 generator forward (the bench's headline leg without its bookkeeping): frames/s over 30 steps.
-Usage: [APAMD_FUSED_NORM=1] python tools/gen_time.py"""
+Usage: python tools/gen_time.py"""
 import os
 import sys
 import time

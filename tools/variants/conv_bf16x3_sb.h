@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16x3_sb(const ConvKParams p) {
     // the second half of the grid (the workgroups that land beside an already running one) starts half a stage late, so that the
     // two workgroups of a CU alternate between DMA wait and multiplication instead of marching in step
     if ((int)blockIdx.x >= (int)gridDim.x / 2) {
-        for (int i = 0; i < p.fn_debug; ++i) __builtin_amdgcn_s_sleep(64);
+        for (int i = 0; i < p.sb_skew; ++i) __builtin_amdgcn_s_sleep(64);
     }
 
     int pgeo[NIT];
