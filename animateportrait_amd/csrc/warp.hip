@@ -12,6 +12,7 @@
 // per channel are coalesced 256-B rows); sample coordinates and the 2x4 tap offsets/weights are
 // computed once per pixel and reused for CG channels.
 #include "common.h"
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -513,6 +514,7 @@ __device__ __forceinline__ PixelTaps pixel_taps(int n, int oy, int ox, const flo
 constexpr int kBwdTileW = 32, kBwdTileH = 16, kBwdPix = kBwdTileW * kBwdTileH;
 constexpr int kBwdWin = 1344;       // window floats per channel (8 channels: 42 KiB; two workgroups per CU with the rest)
 constexpr int kBwdWinW = 48;        // width of a clipped window
+constexpr int kWarpBwdMaxH = 32757, kWarpBwdMaxW = 65525;    // what the 15 + 16 bits of s_xy hold (ap_warp_concat_bwd refuses more)
 
 // ds_add_f32 retires about ONE LANE per clock per CU on gfx950 (measured: 537 M lane-atomics of the 256 x 256 level took
 // 1.3 ms of the launch's 2.2 ms), against 32 lanes per clock for plain LDS reads / writes.  So the accumulation is done
@@ -894,6 +896,12 @@ extern "C" int ap_warp_concat_bwd(const float* gout, const float* motion, const 
                                   ap_stream_t stream) {
     if (!gout || !motion || !flow || !ifmask || !dx) return fail(AP_ERR_INVALID, "warp_concat_bwd: null pointer");
     if (N < 1 || C < 1 || H < 1 || W < 1 || S < 1 || N > 65535) return fail(AP_ERR_INVALID, "warp_concat_bwd: bad sizes");
+    // the tiled kernel packs (y0 + 8) << 16 | (x0 + 8) of a north-west tap (y0 <= H + 1, x0 <= W + 1) under a flag in bit 31,
+    // and both kernels index a plane with an int
+    if (H > kWarpBwdMaxH || W > kWarpBwdMaxW)
+        return fail(AP_ERR_UNSUPPORTED, "warp_concat_bwd: H <= %d and W <= %d are served (got %d x %d)", kWarpBwdMaxH, kWarpBwdMaxW, H, W);
+    if ((long long)H * W > INT_MAX / 2)
+        return fail(AP_ERR_UNSUPPORTED, "warp_concat_bwd: H * W <= %d is served (got %d x %d)", INT_MAX / 2, H, W);
     hipError_t e = hipMemsetAsync(dx, 0, (size_t)N * C * H * W * sizeof(float), (hipStream_t)stream);
     if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "warp_concat_bwd memset: %s", hipGetErrorString(e));
     const char* plain = getenv("APAMD_WARP_BWD_PLAIN");
@@ -932,6 +940,8 @@ extern "C" int ap_warp_concat_fwd_ex(const float* x, const float* x_mean, const 
     if (N < 1 || C < 1 || H < 1 || W < 1 || S < 1) return fail(AP_ERR_INVALID, "warp_concat_fwd: bad sizes");
     if (x_act < 0 || x_act > 2) return fail(AP_ERR_INVALID, "warp_concat_fwd: act %d", x_act);
     if (N > 65535) return fail(AP_ERR_UNSUPPORTED, "warp_concat_fwd: N too large");
+    if ((long long)H * W > INT_MAX / 2)      // pixel and tap offsets inside a plane are ints
+        return fail(AP_ERR_UNSUPPORTED, "warp_concat_fwd: H * W <= %d is served (got %d x %d)", INT_MAX / 2, H, W);
     if ((C % kWarpCG) != 0 && (xs || !out))
         return fail(AP_ERR_UNSUPPORTED, "warp_concat_fwd: the split output needs C %% 8 == 0 (C=%d)", C);
     dim3 grid((H * W + 255) / 256, (C + kWarpCG - 1) / kWarpCG, N);

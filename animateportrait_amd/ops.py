@@ -1320,9 +1320,18 @@ def bias_grad(dy, out=None):
 
 
 def warp_concat_bwd(gout, motion, flow, ifmask, level):
+    """Gradient of warp_concat w.r.t. its feature map: gout (N, 2C, H, W) -> dx (N, C, H, W); the same shape rules as warp_concat."""
+    for t, name in ((gout, 'gout'), (motion, 'motion'), (flow, 'flow'), (ifmask, 'ifmask')):
+        _require_device(t, name)
+    if gout.dim() != 4 or gout.shape[1] < 2 or gout.shape[1] % 2 != 0:
+        raise ValueError('warp_concat_bwd: gout %s is not the gradient of a (N, 2C, H, W) concat' % (tuple(gout.shape),))
     n, c2, h, w = gout.shape
     c = c2 // 2
-    s = motion.shape[1]
+    s = motion.shape[1] if motion.dim() == 4 else -1
+    if motion.shape != (n, s, s, 2) or flow.shape != (n, 2, s, s) or ifmask.shape != (n, 1, s, s):
+        raise ValueError('warp_concat_bwd: motion/flow/ifmask shapes %s %s %s' % (motion.shape, flow.shape, ifmask.shape))
+    if h != s >> level or w != s >> level:
+        raise ValueError('warp_concat_bwd: level %d expects %d px features, got %dx%d' % (level, s >> level, h, w))
     dx = torch.empty((n, c, h, w), dtype=torch.float32, device=gout.device)
     C.check(C.lib().ap_warp_concat_bwd(_ptr(gout), _ptr(motion), _ptr(flow), _ptr(ifmask), _ptr(dx), n, c, h, w, s,
                                        1.0 / (1 << level), _stream()), 'warp_concat_bwd')

@@ -259,7 +259,10 @@ int ap_instnorm_apply(const float* x, const float* mean, const float* rstd, int3
  * out[:, C:2C] = where(mask_L > 0.5, grid_sample(x, grid(flow_L)), -1)
  * with motion_L / flow_L / mask_L the align_corners=True bilinear resizes of the full-resolution
  * motion (N,S,S,2) / flow/2^level (N,2,S,S) / ifmask (N,1,S,S) to x's H x W, computed on the fly.
- * x may be a raw conv output with (mean, rstd, act) applied per tap (act(IN(x)) is what is sampled). */
+ * x may be a raw conv output with (mean, rstd, act) applied per tap (act(IN(x)) is what is sampled).
+ * H, W and S are independent: any N, C, H, W, S >= 1 with N <= 65535 and H * W <= INT_MAX / 2 is served (H == W == S reads
+ * the maps directly, every other combination resizes them, S < H included; a 1-pixel axis follows the max(size - 1, 1) rule
+ * of warp_acc_flow).  Larger maps are refused with AP_ERR_UNSUPPORTED; this holds for every ap_warp_concat_fwd* entry. */
 int ap_warp_concat_fwd(const float* x, const float* x_mean, const float* x_rstd, int32_t x_act,
                        const float* motion, const float* flow, const float* ifmask,
                        float* out, int32_t N, int32_t C, int32_t H, int32_t W, int32_t S,
@@ -473,7 +476,9 @@ int ap_bias_grad(const float* dy, int32_t N, int32_t C, int32_t HW, float* db, a
  * C is small (the 1-channel output layers); workspace: ap_bias_grad_workspace_floats() floats */
 int64_t ap_bias_grad_workspace_floats(int32_t N, int32_t C, int32_t HW);
 int ap_bias_grad_ws(const float* dy, int32_t N, int32_t C, int32_t HW, float* workspace, float* db, ap_stream_t stream);
-/* backward of ap_warp_concat_fwd w.r.t. x (gout: N x 2C x H x W -> dx: N x C x H x W, zeroed inside) */
+/* backward of ap_warp_concat_fwd w.r.t. x (gout: N x 2C x H x W -> dx: N x C x H x W, zeroed inside: every element of dx
+ * is written).  Same independent H, W, S as the forward, with H <= 32757, W <= 65525 and H * W <= INT_MAX / 2; beyond that
+ * AP_ERR_UNSUPPORTED is returned before anything touches dx. */
 int ap_warp_concat_bwd(const float* gout, const float* motion, const float* flow, const float* ifmask,
                        float* dx, int32_t N, int32_t C, int32_t H, int32_t W, int32_t S, float flow_scale,
                        ap_stream_t stream);
