@@ -1,20 +1,25 @@
-"""Dataset registry (Module2/data/__init__.py:47-91).  The reference's file-based datasets
-(umlvd_ifw, umlvdfw_test) read a Data/ tree that is not in the tree and are outside the hot path; the
-``synthetic`` mode produces batches with the same dict keys / shapes / value ranges."""
+"""Dataset registry (Module2/data/__init__.py:47-91).
+
+``umlvd_ifw`` is the reference's training dataset on its own file tree, with the batch prepared on the device
+(umlvd_ifw_dataset.py); ``synthetic`` produces batches with the same dict keys / shapes / value ranges from a seed and needs
+no files.  The reference's test-time dataset (umlvdfw_test) is not here: test.py drives the generator from frames."""
 from .synthetic_dataset import SyntheticDataset
 
 
 def find_dataset_using_name(name):
     if name == 'synthetic':
         return SyntheticDataset
-    raise NotImplementedError('dataset_mode [%s] is outside the MI355X hot path; use --dataset_mode synthetic or feed '
-                              'model.set_input() with batches from the reference data layer' % name)
+    if name == 'umlvd_ifw':
+        from .umlvd_ifw_dataset import UMLVDIFWDataset
+        return UMLVDIFWDataset
+    raise NotImplementedError('dataset_mode [%s] is not implemented; use --dataset_mode umlvd_ifw (the reference\'s training '
+                              'tree) or --dataset_mode synthetic' % name)
 
 
 def get_option_setter(name):
-    if name == 'synthetic':
-        return SyntheticDataset.modify_commandline_options
-    return lambda parser, is_train: parser   # the model sets dataset_mode=umlvd_ifw by default; tolerate it at parse time
+    if name in ('synthetic', 'umlvd_ifw'):
+        return find_dataset_using_name(name).modify_commandline_options
+    return lambda parser, is_train: parser   # unknown modes fail in create_dataset, with the message above
 
 
 def create_dataset(opt):
