@@ -25,6 +25,19 @@ SIGNATURES = {
     'apd_image_prep_u8': (ctypes.c_int, [ctypes.POINTER(ApdImagePrep)] + [ctypes.c_void_p] * 9),
 }
 
+# Added after the first release of data ABI 1 without changing any call above, so the version number stays: a library
+# that predates them is recognised by the missing symbol.
+_i32, _ptr = ctypes.c_int32, ctypes.c_void_p
+SIGNATURES.update({
+    'apd_landmark_map_ok': (ctypes.c_int32, [_ptr] * 4 + [_i32] * 8),
+    'apd_landmark_map': (ctypes.c_int, [_ptr] * 3 + [_i32] * 8 + [ctypes.c_float, ctypes.c_float, _ptr, _ptr]),
+    'apd_landmark_marks_ok': (ctypes.c_int32, [_ptr] * 4 + [_i32] * 6),
+    'apd_landmark_marks': (ctypes.c_int, [_ptr] * 3 + [_i32] * 6 + [_ptr, _ptr]),
+    'apd_frames_to_u8_ok': (ctypes.c_int32, [_ptr] * 2 + [_i32] * 4),
+    'apd_frames_to_u8': (ctypes.c_int, [_ptr] + [_i32] * 4 + [_ptr, _ptr]),
+})
+MAX_SEGMENTS, MAX_RADIUS, MAX_THICKNESS, MAX_MAP, MAX_POINTS = 128, 31, 16, 1024, 1024
+
 _lib = None
 _lock = threading.Lock()
 
@@ -40,6 +53,9 @@ def lib():
                                        'There is no CPU fallback inside --data_prep device.' % LIB_PATH)
                 l = ctypes.CDLL(LIB_PATH)
                 for name, (res, args) in SIGNATURES.items():
+                    if not hasattr(l, name):
+                        raise RuntimeError('animateportrait_amd: %s is stale: it lacks %s. Rebuild it '
+                                           '(make -C animateportrait_amd/csrc)' % (LIB_PATH, name))
                     fn = getattr(l, name)
                     fn.restype = res
                     fn.argtypes = args

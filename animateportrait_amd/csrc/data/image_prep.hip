@@ -11,19 +11,27 @@
 #include <math.h>
 
 #include "../../../include/animateportrait_data.h"
+#include "apd_common.h"
+
+namespace apd {
+
+thread_local char g_err[256];
+
+int fail(int code, const char* fmt, long a, long b, long c, long d) {
+    snprintf(g_err, sizeof(g_err), fmt, a, b, c, d);
+    return code;
+}
+
+}  // namespace apd
 
 namespace {
+
+using apd::fail;
+using apd::g_err;
 
 constexpr int TW = 64, TH = 16, THREADS = 256;
 constexpr int PRECISION_BITS = 32 - 8 - 2;       // Pillow: Resample.c
 constexpr int MAX_LDS_BYTES = 48 * 1024;
-
-thread_local char g_err[256];
-
-int fail(int code, const char* fmt, long a = 0, long b = 0, long c = 0, long d = 0) {
-    snprintf(g_err, sizeof(g_err), fmt, a, b, c, d);
-    return code;
-}
 
 // Pillow's ksize for one axis; 0 when the axis keeps its size (the pass is skipped)
 int expected_taps(int in, int out) {

@@ -1,8 +1,9 @@
 """Dataset registry (Module2/data/__init__.py:47-91).
 
 ``umlvd_ifw`` is the reference's training dataset on its own file tree, with the batch prepared on the device
-(umlvd_ifw_dataset.py); ``synthetic`` produces batches with the same dict keys / shapes / value ranges from a seed and needs
-no files.  The reference's test-time dataset (umlvdfw_test) is not here: test.py drives the generator from frames."""
+(umlvd_ifw_dataset.py); ``umlvdfw_test`` is its test-time dataset on the same tree (umlvdfw_test_dataset.py: photo,
+both landmark maps, motion grid and static warp per batch, the default of ``--model geomcgt_ifw_test``); ``synthetic``
+produces batches with the same dict keys / shapes / value ranges from a seed and needs no files."""
 from .synthetic_dataset import SyntheticDataset
 
 
@@ -12,12 +13,15 @@ def find_dataset_using_name(name):
     if name == 'umlvd_ifw':
         from .umlvd_ifw_dataset import UMLVDIFWDataset
         return UMLVDIFWDataset
+    if name == 'umlvdfw_test':
+        from .umlvdfw_test_dataset import UMLVDFWTestDataset
+        return UMLVDFWTestDataset
     raise NotImplementedError('dataset_mode [%s] is not implemented; use --dataset_mode umlvd_ifw (the reference\'s training '
-                              'tree) or --dataset_mode synthetic' % name)
+                              'tree), umlvdfw_test (its test tree) or --dataset_mode synthetic' % name)
 
 
 def get_option_setter(name):
-    if name in ('synthetic', 'umlvd_ifw'):
+    if name in ('synthetic', 'umlvd_ifw', 'umlvdfw_test'):
         return find_dataset_using_name(name).modify_commandline_options
     return lambda parser, is_train: parser   # unknown modes fail in create_dataset, with the message above
 

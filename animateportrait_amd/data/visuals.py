@@ -1,0 +1,140 @@
+"""Device stages of the test-time item and of test.py's PNG sink (libapdata.so, include/animateportrait_data.h):
+
+  * ``landmark_map``   draw2(op = 0 | 1) of Module2/data/umlvdfw_test_dataset.py:34-52 for a batch (apd_landmark_map),
+  * ``landmark_marks`` get_lmvis of Module2/models/geomcgt_ifw_test_model.py:232-251 per sample (apd_landmark_marks),
+  * ``frames_to_u8``   tensor2im of Module2/util/util.py:9-29 for a batch (apd_frames_to_u8), into device memory or into a
+    pinned host buffer the kernel writes directly,
+  * ``save_png_batch`` the sink: one launch per visual, one stream synchronisation, PNG encoding on a thread pool.
+
+A missing library or a refused call raises; nothing here falls back to the host."""
+import concurrent.futures
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from .. import _dataapi as D
+
+PNG_THREADS = 16          # a constant, not os.cpu_count(): the encoders share the machine with the data pool
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _device_f32(t, what, dims):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dim() == dims):
+        raise ValueError('%s: expected a %d-d device tensor' % (what, dims))
+    return t.detach().float().contiguous()
+
+
+def load_lookup(path):
+    """faceLmarkLookup.npy: the (S, 2) integer table of landmark pairs draw2(op=1) joins, read at run time as the reference
+    reads it (umlvdfw_test_dataset.py:33)."""
+    if not os.path.exists(path):
+        raise FileNotFoundError('--draw_op 1 joins the landmark pairs of %s, which does not exist: copy faceLmarkLookup.npy '
+                                'from the reference\'s Module2/ or name it with --lmark_lookup' % path)
+    seg = np.load(path)
+    if seg.ndim != 2 or seg.shape[1] != 2 or seg.dtype.kind not in 'iu':
+        raise ValueError('%s: expected an (S, 2) integer table, found %s %s' % (path, seg.dtype, seg.shape))
+    return np.ascontiguousarray(seg.astype(np.int32))
+
+
+_SEG = {}        # (device, table bytes) -> device copy
+
+
+def landmark_map(lm, segments, height, width, radius, thickness, op, lo=-1.0, hi=1.0):
+    """lm (N, P, 2) device (x, y); segments (S, 2) int host array or None -> (N, 1, height, width) float32 in {lo, hi}."""
+    lm = _device_f32(lm, 'landmark_map', 3)
+    n, p, _ = lm.shape
+    host = np.zeros((0, 2), np.int32) if segments is None or op == 0 else np.ascontiguousarray(np.asarray(segments, dtype=np.int32))
+    s = int(host.shape[0])
+    dev = None
+    if s:
+        key = (str(lm.device), host.tobytes())
+        if key not in _SEG:
+            _SEG[key] = torch.from_numpy(host).to(lm.device)
+        dev = _SEG[key]
+    out = torch.empty((n, 1, height, width), dtype=torch.float32, device=lm.device)
+    with torch.cuda.device(lm.device):
+        D.check(D.lib().apd_landmark_map(_p(lm), _p(dev), host.ctypes.data_as(ctypes.c_void_p) if s else None, n, p, s, height, width,
+                                         int(radius), int(thickness), int(op), lo, hi, _p(out), _stream(lm.device)), 'landmark_map')
+    return out
+
+
+def landmark_marks(frames, lm, win, hradius=3):
+    """frames (N, C, H, W) device, C in {1, 3}; lm (N, P, 2); win (N, 4) [x1, x2, y1, y2] (tensor, array or list) ->
+    (N, 3, H, W): every sample carries its own marks."""
+    frames = _device_f32(frames, 'landmark_marks', 4)
+    n, c, h, w = frames.shape
+    lm = _device_f32(lm.to(frames.device), 'landmark_marks', 3)
+    win = torch.as_tensor(np.asarray(win.cpu() if torch.is_tensor(win) else win), dtype=torch.int32).reshape(-1, 4)
+    if lm.shape[0] != n or win.shape[0] != n:
+        raise ValueError('landmark_marks: %d frames, %d landmark sets, %d windows' % (n, lm.shape[0], win.shape[0]))
+    win = win.to(frames.device).contiguous()
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        D.check(D.lib().apd_landmark_marks(_p(frames), _p(lm), _p(win), n, c, lm.shape[1], h, w, int(hradius), _p(out),
+                                           _stream(frames.device)), 'landmark_marks')
+    return out
+
+
+_PINNED = {}      # (shape, device, slot) -> pinned uint8 buffer, reused
+
+
+def pinned_u8(shape, device, slot=0):
+    key = (tuple(shape), str(device), slot)
+    if key not in _PINNED:
+        _PINNED[key] = torch.empty(tuple(shape), dtype=torch.uint8).pin_memory()
+    return _PINNED[key]
+
+
+def frames_to_u8(frames, out=None, slot=0):
+    """frames (N, C, H, W) device float32, C in {1, 3} -> (N, H, W, 3) uint8.  ``out``: None = the pinned host buffer of this
+    (shape, device, slot), written by the kernel itself (synchronise the stream before reading it); 'device' = a fresh
+    device tensor; or a contiguous uint8 tensor of that shape, on the device or pinned."""
+    frames = _device_f32(frames, 'frames_to_u8', 4)
+    n, c, h, w = frames.shape
+    if out is None:
+        out = pinned_u8((n, h, w, 3), frames.device, slot)
+    elif isinstance(out, str) and out == 'device':
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=frames.device)
+    if tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError('frames_to_u8: out must be a contiguous (%d, %d, %d, 3) uint8 tensor' % (n, h, w))
+    if not out.is_cuda and not out.is_pinned():
+        raise ValueError('frames_to_u8: a host destination must be pinned')
+    with torch.cuda.device(frames.device):
+        D.check(D.lib().apd_frames_to_u8(_p(frames), n, c, h, w, _p(out), _stream(frames.device)), 'frames_to_u8')
+    return out
+
+
+_POOL = None
+
+
+def png_pool():
+    global _POOL
+    if _POOL is None:
+        _POOL = concurrent.futures.ThreadPoolExecutor(max_workers=PNG_THREADS)
+    return _POOL
+
+
+def save_png_batch(visuals, names):
+    """visuals: {label: (N, C, H, W) device tensor}; names: {label: [N paths]}.  One apd_frames_to_u8 launch per visual into
+    its pinned buffer, one synchronisation, then PIL encodes on the pool.  Returns the number of files written."""
+    from PIL import Image
+    if not visuals:
+        return 0
+    device = next(iter(visuals.values())).device
+    staged = [(label, frames_to_u8(t, slot=label)) for label, t in visuals.items()]
+    torch.cuda.current_stream(device).synchronize()
+    jobs = [(buf.numpy()[i], names[label][i]) for label, buf in staged for i in range(buf.shape[0])]
+
+    def save(job):
+        Image.fromarray(job[0]).save(job[1])
+    list(png_pool().map(save, jobs))
+    return len(jobs)

@@ -105,10 +105,16 @@ class GeomCGTIFWTestModel(BaseModel):
         if self.aux['netF'] is not None:
             self.iw_flow, self.real_A_if_mask = losses.flow_network_warp(                       # :62-76, :270-271
                 self.aux['netF'], self.real_A, self.real_A_lm_68[:, :68], self.target_B_lm_68[:, :68])
-        else:
+        elif 'iw_flow' in input and 'if_mask' in input:
             self.iw_flow, self.real_A_if_mask = input['iw_flow'].to(dev), input['if_mask'].to(dev)
+        else:
+            raise RuntimeError('geomcgt_ifw_test: the input carries no iw_flow / if_mask and no flow network is attached: load '
+                               'the intrinsic-flow checkpoint (netF) into model.aux[\'netF\']')
         self._matte_in = None
         if self.aux['modnet'] is None:
+            if 'matte' not in input and 'mask' not in input:
+                raise RuntimeError('geomcgt_ifw_test: the input carries no matte / mask and no matting network is attached: '
+                                   'load the MODNet checkpoint into model.aux[\'modnet\']')
             self._matte_in = (input['matte'] if 'matte' in input else input['mask']).to(dev)
 
     # ------------------------------------------------------------------------------------------------ forward
@@ -144,25 +150,11 @@ class GeomCGTIFWTestModel(BaseModel):
         if hasattr(self, 'target_B_lm_68') and hasattr(self, 'winB'):
             self.fake_B_vis = self.get_lmvis(self.fake_B, self.target_B_lm_68, self.winB)
 
-    def get_lmvis(self, tensor_im, lm, win, hradius=3):                             # :232-251 (sample 0, as there)
-        vis = tensor_im.detach().clone()
-        if vis.shape[1] == 1:
-            vis = vis.repeat(1, 3, 1, 1)
-        pts = lm.detach().cpu().numpy()
-        win = win.cpu().numpy() if torch.is_tensor(win) else win
-
-        def mark(y0, y1, x0, x1):
-            vis[:, 0, y0:y1, x0:x1] = 1
-            vis[:, 1:, y0:y1, x0:x1] = -1
-        for k in range(lm.shape[1]):
-            x, y = int(round(float(pts[0, k, 0]))), int(round(float(pts[0, k, 1])))
-            mark(y - hradius, y + hradius, x - hradius, x + hradius)
-        x1, x2, y1, y2 = (int(win[0][i]) for i in range(4))
-        mark(y1 - hradius, y1 + hradius, x1 - hradius, x2 + hradius)
-        mark(y2 - hradius, y2 + hradius, x1 - hradius, x2 + hradius)
-        mark(y1 - hradius, y2 + hradius, x1 - hradius, x1 + hradius)
-        mark(y1 - hradius, y2 + hradius, x2 - hradius, x2 + hradius)
-        return vis
+    def get_lmvis(self, tensor_im, lm, win, hradius=3):                             # :232-251
+        """The frame with its landmarks and window marked red, one apd_landmark_marks launch for the batch.  The reference
+        is written for batch size 1; here every sample gets its own marks, and boxes are clipped to the image."""
+        from ..data import visuals
+        return visuals.landmark_marks(tensor_im, lm, win, hradius)
 
     def optimize_parameters(self):
         pass                                                                         # test-time model

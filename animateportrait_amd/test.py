@@ -1,6 +1,8 @@
 """Inference entry point -- counterpart of Module2/test.py:38-66: build the model, load ``G_A``, run the
-generator over the dataset and write the frames (``.npy`` per frame; the PNG/HTML writers of the reference's
-util/visualizer.py are outside the hot path)."""
+generator over the dataset and write the frames.  ``--save_format npy`` (the default) writes ``fake_B`` as one ``.npy`` per
+frame; ``png`` writes every visual of ``get_current_visuals()`` as ``<stem>_<label>.png``, the names the reference's
+util/visualizer.py save_images gives, through the device sink of data/visuals.py; ``both`` does both.  The HTML page of the
+reference's visualizer is not written."""
 import os
 
 import numpy as np
@@ -10,13 +12,33 @@ from .data import create_dataset
 from .models import create_model
 from .options.base_options import TestOptions
 
+SAVE_FORMATS = ('npy', 'png', 'both')
 
-def main(argv=None):
-    opt = TestOptions().parse(argv)
+
+def parse(argv=None):
+    """TestOptions plus --save_format, which is this entry point's own flag"""
+    options = TestOptions()
+    initialize = options.initialize
+
+    def with_save_format(p):
+        p = initialize(p)
+        p.add_argument('--save_format', type=str, default='npy', choices=SAVE_FORMATS,
+                       help='npy: fake_B per frame as .npy; png: every visual as <stem>_<label>.png; both')
+        return p
+    options.initialize = with_save_format
+    return options.parse(argv)
+
+
+def main(argv=None, prepare_model=None):
+    """``prepare_model(model)`` runs after the model is built and before setup(): the place to attach the frozen third-party
+    networks (model.aux) the reference loads from checkpoints this project does not ship."""
+    opt = parse(argv)
     opt.num_threads, opt.serial_batches, opt.no_flip = 0, True, True     # test.py:41-45
     torch.cuda.set_device(opt.gpu_ids[0])
     dataset = create_dataset(opt)
     model = create_model(opt)
+    if prepare_model is not None:
+        prepare_model(model)
     model.setup(opt)       # loads '<epoch>_net_G_A.pth'; a missing file is an error (test.py:48) unless --allow_random_init
     if opt.eval:
         model.eval()
@@ -28,10 +50,17 @@ def main(argv=None):
             break
         model.set_input(data)
         model.test()
-        fake = model.fake_B.detach().cpu().numpy()
-        for i, path in enumerate(model.get_image_paths()):
-            np.save(os.path.join(out_dir, os.path.basename(str(path)) + '_fake_B.npy'), fake[i])
-            n += 1
+        paths = [str(p) for p in model.get_image_paths()]
+        if opt.save_format in ('npy', 'both'):
+            fake = model.fake_B.detach().cpu().numpy()
+            for i, path in enumerate(paths):
+                np.save(os.path.join(out_dir, os.path.basename(path) + '_fake_B.npy'), fake[i])
+        if opt.save_format in ('png', 'both'):
+            from .data import visuals
+            stems = [os.path.splitext(os.path.basename(path))[0] for path in paths]
+            shown = {label: t for label, t in model.get_current_visuals().items() if torch.is_tensor(t) and t.dim() == 4}
+            visuals.save_png_batch(shown, {label: [os.path.join(out_dir, '%s_%s.png' % (s, label)) for s in stems] for label in shown})
+        n += len(paths)
     print('wrote %d frames to %s' % (n, out_dir))
 
 

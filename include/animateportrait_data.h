@@ -65,6 +65,59 @@ int apd_image_prep_u8(const apd_image_prep* d, const uint8_t* src, const int32_t
                       const int32_t* hbounds, const int32_t* hweights, const int32_t* vbounds, const int32_t* vweights,
                       const float* lut, float* out, void* stream);
 
+/* ---- the test-time item (data/umlvdfw_test_dataset.py) and the PNG sink of test.py.  Added without changing any call
+ * above, so APD_ABI_VERSION stays 1; a binding finds a library that predates them by the missing symbol. */
+
+#define APD_MAX_SEGMENTS 128   /* contour segments per landmark map */
+#define APD_MAX_RADIUS 31      /* disc radius */
+#define APD_MAX_THICKNESS 16   /* line thickness */
+#define APD_MAX_MAP 1024       /* landmark map height / width */
+#define APD_MAX_POINTS 1024    /* landmarks per sample */
+
+/* draw2(height, width, lands, radius, thickness, op = 0 | 1) (Module2/data/umlvdfw_test_dataset.py:34-52) for a batch.
+ *   lm        device (N, P, 2) float32 (x, y); rounded half-to-even to int as np.round(...).astype(int) does, then clamped
+ *             to +-2^20 (NaN goes to -2^20)
+ *   seg       device (S, 2) int32 landmark indices (faceLmarkLookup.npy); may be null when S == 0 or op == 0
+ *   seg_host  the same table on the host: every index is checked against P here, before the launch.  The kernel clamps
+ *             what it reads from `seg` into [0, P), so a device table that differs gives wrong pixels, never a wild access.
+ *   out       device (N, 1, H, W) float32, every element written: `hi` on a mark, `lo` elsewhere (no memset needed)
+ * op 0: the union of filled cv2.circle(radius) discs -- bit-equal to ap_landmark_discs.
+ * op 1: the discs, then the union of cv2.line(start, end, color, thickness) over the segments by OpenCV 4.2's ThickLine
+ *       rule as oracle/cv_raster.thick_line restates it: the quad through FillConvexPoly at 16.16 fixed point plus a filled
+ *       circle of radius (thickness + 1) >> 1 at both ends.  thickness 1 follows the same quad rule (cv2 itself draws a
+ *       Bresenham line there; the reference uses 2 and 4).
+ * Marks are clipped to the image; a point or segment wholly outside draws nothing.
+ * Served: N 1..65535, P 1..APD_MAX_POINTS, S 0..APD_MAX_SEGMENTS, H, W 1..APD_MAX_MAP, radius 0..APD_MAX_RADIUS,
+ * thickness 1..APD_MAX_THICKNESS.  apd_landmark_map_ok needs no device and checks everything but the device pointers'
+ * contents. */
+int32_t apd_landmark_map_ok(const float* lm, const int32_t* seg, const int32_t* seg_host, const float* out, int32_t N,
+                            int32_t P, int32_t S, int32_t H, int32_t W, int32_t radius, int32_t thickness, int32_t op);
+int apd_landmark_map(const float* lm, const int32_t* seg, const int32_t* seg_host, int32_t N, int32_t P, int32_t S,
+                     int32_t H, int32_t W, int32_t radius, int32_t thickness, int32_t op, float lo, float hi, float* out,
+                     void* stream);
+
+/* get_lmvis (Module2/models/geomcgt_ifw_test_model.py:232-251) per sample.
+ *   frames  device (N, C, H, W) float32, C = 1 or 3     lm  device (N, P, 2) float32 (x, y)
+ *   win     device (N, 4) int32: x1, x2, y1, y2          out device (N, 3, H, W) float32, must not overlap frames
+ * out = frames (grey tiled to 3 channels) with channel 0 = 1 and channels 1, 2 = -1 inside
+ *   [y - h, y + h) x [x - h, x + h) around every rounded (half to even) landmark, h = hradius, and the four bars
+ *   rows [y1 - h, y1 + h) and [y2 - h, y2 + h) over columns [x1 - h, x2 + h); columns [x1 - h, x1 + h) and
+ *   [x2 - h, x2 + h) over rows [y1 - h, y2 + h).  Every box is clipped to the image.
+ * Served: N 1..65535, P 1..APD_MAX_POINTS, H, W 1..4096, hradius 0..64. */
+int32_t apd_landmark_marks_ok(const float* frames, const float* lm, const int32_t* win, const float* out, int32_t N,
+                              int32_t C, int32_t P, int32_t H, int32_t W, int32_t hradius);
+int apd_landmark_marks(const float* frames, const float* lm, const int32_t* win, int32_t N, int32_t C, int32_t P,
+                       int32_t H, int32_t W, int32_t hradius, float* out, void* stream);
+
+/* tensor2im (Module2/util/util.py:9-29) for a batch: src device (N, C, H, W) float32, C = 1 or 3 -> dst (N, H, W, 3) uint8,
+ * grey tiled to three channels.  byte = (uint8)((x + 1) / 2 * 255) in unfused float32, truncated.  Results below 0 (and
+ * NaN) give 0, results of 255 and above give 255: numpy's cast is undefined there, this contract is not.
+ * dst is 4-byte aligned and is either device memory or pinned host memory mapped for the device (hipHostMalloc): the
+ * call asks the runtime which (hipPointerGetAttributes) and refuses any other pointer.  The host sees the bytes once the
+ * stream has been synchronised.  Served: N, H, W >= 1 with N H W 3 < 2^31. */
+int32_t apd_frames_to_u8_ok(const float* src, const uint8_t* dst, int32_t N, int32_t C, int32_t H, int32_t W);
+int apd_frames_to_u8(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, uint8_t* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
