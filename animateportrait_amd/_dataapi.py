@@ -38,6 +38,16 @@ SIGNATURES.update({
 })
 MAX_SEGMENTS, MAX_RADIUS, MAX_THICKNESS, MAX_MAP, MAX_POINTS = 128, 31, 16, 1024, 1024
 
+# the device PNG encoder (csrc/data/png_encode.hip), added the same way
+_i64 = ctypes.c_int64
+SIGNATURES.update({
+    'apd_png_bound': (_i64, [_i32] * 3),
+    'apd_png_workspace_bytes': (_i64, [_i32] * 4),
+    'apd_png_encode_ok': (ctypes.c_int32, [_ptr] * 4 + [_i32] * 5 + [_i64] * 2),
+    'apd_png_encode': (ctypes.c_int, [_ptr] + [_i32] * 5 + [_ptr, _i64, _ptr, _ptr, _i64, _ptr]),
+})
+MAX_PNG_SIDE = 2048
+
 _lib = None
 _lock = threading.Lock()
 

@@ -15,16 +15,9 @@
 namespace {
 
 using apd::fail;
+using apd::to_byte;          // apd_common.h: shared with png_encode.hip
 
 constexpr int THREADS = 256;
-
-// ((x + 1) / 2 * 255) truncated, as numpy computes it in float32; this file is compiled with -ffp-contract=off
-__device__ __forceinline__ unsigned to_byte(float x) {
-    const float v = (x + 1.0f) / 2.0f * 255.0f;
-    if (!(v > 0.0f)) return 0u;              // also NaN
-    if (v >= 255.0f) return 255u;
-    return (unsigned)(int)v;
-}
 
 // byte b of the destination: pixel b / 3, channel b % 3
 __device__ __forceinline__ unsigned byte_at(const float* __restrict__ src, long long b, int C, long long plane) {

@@ -4,7 +4,9 @@
   * ``landmark_marks`` get_lmvis of Module2/models/geomcgt_ifw_test_model.py:232-251 per sample (apd_landmark_marks),
   * ``frames_to_u8``   tensor2im of Module2/util/util.py:9-29 for a batch (apd_frames_to_u8), into device memory or into a
     pinned host buffer the kernel writes directly,
-  * ``save_png_batch`` the sink: one launch per visual, one stream synchronisation, PNG encoding on a thread pool.
+  * ``save_png_batch`` the sink: one launch per visual, one stream synchronisation, PNG encoding on a thread pool,
+  * ``encode_png_batch`` complete PNG files made on the device (apd_png_encode); ``save_png_batch(encoder='device')`` writes
+    them, and the pool is left with the write() calls.
 
 A missing library or a refused call raises; nothing here falls back to the host."""
 import concurrent.futures
@@ -123,13 +125,55 @@ def png_pool():
     return _POOL
 
 
-def save_png_batch(visuals, names):
-    """visuals: {label: (N, C, H, W) device tensor}; names: {label: [N paths]}.  One apd_frames_to_u8 launch per visual into
-    its pinned buffer, one synchronisation, then PIL encodes on the pool.  Returns the number of files written."""
-    from PIL import Image
+_PNG = {}         # (N, C, H, W, channels, device, slot) -> (pinned file slots, pinned sizes, device workspace), reused
+
+
+def encode_png_batch(frames, channels=3, slot=0):
+    """frames (N, C, H, W) device float32, C in {1, 3} -> (buf (N, apd_png_bound) uint8, sizes (N,) int32), both pinned host
+    buffers of this (shape, channels, device, slot) that the kernels write themselves: after the stream has been synchronised,
+    frame i's complete PNG file is ``buf[i, :sizes[i]]``.  channels 3: RGB, grey tiled; channels 1: greyscale, C must be 1."""
+    frames = _device_f32(frames, 'encode_png_batch', 4)
+    n, c, h, w = frames.shape
+    lib = D.lib()
+    key = (n, c, h, w, int(channels), str(frames.device), slot)
+    if key not in _PNG:
+        bound, ws = lib.apd_png_bound(h, w, int(channels)), lib.apd_png_workspace_bytes(n, h, w, int(channels))
+        if bound < 0 or ws < 0:
+            raise RuntimeError('libapdata png_encode refused: %s' % D.last_error())
+        _PNG[key] = (torch.empty((n, bound), dtype=torch.uint8).pin_memory(), torch.zeros((n,), dtype=torch.int32).pin_memory(),
+                     torch.empty((ws,), dtype=torch.uint8, device=frames.device))
+    buf, sizes, ws = _PNG[key]
+    with torch.cuda.device(frames.device):
+        D.check(lib.apd_png_encode(_p(frames), n, c, h, w, int(channels), _p(buf), buf.shape[1], _p(sizes), _p(ws), ws.numel(),
+                                   _stream(frames.device)), 'png_encode')
+    return buf, sizes
+
+
+PNG_ENCODERS = ('host', 'device')
+
+
+def save_png_batch(visuals, names, encoder='host'):
+    """visuals: {label: (N, C, H, W) device tensor}; names: {label: [N paths]}.  ``encoder='host'``: one apd_frames_to_u8 launch
+    per visual into its pinned buffer, one synchronisation, then PIL encodes on the pool.  ``encoder='device'``: one
+    apd_png_encode call per visual, one synchronisation, then the pool only writes the files.  Returns the number of files
+    written."""
+    if encoder not in PNG_ENCODERS:
+        raise ValueError('save_png_batch: encoder %r, served: %s' % (encoder, ' and '.join(PNG_ENCODERS)))
     if not visuals:
         return 0
     device = next(iter(visuals.values())).device
+    if encoder == 'device':
+        staged = [(label, encode_png_batch(t, slot=label)) for label, t in visuals.items()]
+        torch.cuda.current_stream(device).synchronize()
+        files = [(buf.numpy()[i, :size], names[label][i])
+                 for label, (buf, sizes) in staged for i, size in enumerate(sizes.tolist())]
+
+        def write(job):
+            with open(job[1], 'wb') as f:
+                f.write(job[0])
+        list(png_pool().map(write, files))
+        return len(files)
+    from PIL import Image
     staged = [(label, frames_to_u8(t, slot=label)) for label, t in visuals.items()]
     torch.cuda.current_stream(device).synchronize()
     jobs = [(buf.numpy()[i], names[label][i]) for label, buf in staged for i in range(buf.shape[0])]

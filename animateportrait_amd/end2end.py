@@ -115,7 +115,42 @@ def make_parser():
     ap.add_argument('--triangulate', choices=('host', 'device'), default='host',
                     help='where the motion grids\' Delaunay triangulation runs: scipy on the CPU per frame, or ap_delaunay on the GPU '
                          '(the landmark sequence is then uploaded once and no per-frame work is left on the host)')
+    ap.add_argument('--png_encoder', choices=('host', 'device'), default='host',
+                    help='who makes the frame PNGs: PIL on the host, one frame at a time, or apd_png_encode on the GPU in batches '
+                         'of --batch (the same pixels in larger files; the host only writes them)')
+    ap.add_argument('--png_channels', type=int, choices=(1, 3), default=3,
+                    help='with --png_encoder device: 3 = RGB files as the host writes them, 1 = greyscale files (1-channel frames only)')
     return ap
+
+
+def write_frames(frames, fdir, encoder='host', batch=16, channels=3):
+    """frames (T, C, H, W) -> <fdir>/%05d.png.  'host': tensor2im + PIL per frame.  'device': the frames are encoded where they
+    are, --batch at a time (data/visuals.encode_png_batch), two pinned buffers in turn so that a batch is written to disk while
+    the next is encoded."""
+    if encoder == 'host':
+        from PIL import Image
+        for k in range(frames.shape[0]):
+            Image.fromarray(tensor2im(frames[k])).save(os.path.join(fdir, '%05d.png' % k))
+        return
+    from .data import visuals
+    if not frames.is_cuda:
+        frames = frames.cuda()
+
+    def write(job):
+        with open(job[1], 'wb') as f:
+            f.write(job[0])
+    pending = None
+    for turn, k0 in enumerate(range(0, frames.shape[0], batch)):
+        buf, sizes = visuals.encode_png_batch(frames[k0:k0 + batch], channels=channels, slot='clip%d' % (turn & 1))
+        done = torch.cuda.Event()
+        done.record()
+        if pending is not None:
+            list(pending)                 # the other buffer's files are on disk before it is encoded into again (next turn)
+        done.synchronize()
+        pending = visuals.png_pool().map(write, [(buf.numpy()[i, :size], os.path.join(fdir, '%05d.png' % (k0 + i)))
+                                                 for i, size in enumerate(sizes.tolist())])
+    if pending is not None:
+        list(pending)
 
 
 def main(argv=None):
@@ -155,9 +190,7 @@ def main(argv=None):
     frames = stream.ClipStreamer(model, batch=a.batch, triangulate=a.triangulate).run(photo, lm0, seq, matte=matte)
     fdir = os.path.join(a.out, 'frames')
     os.makedirs(fdir, exist_ok=True)
-    from PIL import Image
-    for k in range(frames.shape[0]):
-        Image.fromarray(tensor2im(frames[k])).save(os.path.join(fdir, '%05d.png' % k))
+    write_frames(frames, fdir, a.png_encoder, a.batch, a.png_channels)
     print('wrote %d frames to %s' % (frames.shape[0], fdir))
     ffmpeg = shutil.which('ffmpeg')
     if ffmpeg is None:

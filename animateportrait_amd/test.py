@@ -1,8 +1,9 @@
 """Inference entry point -- counterpart of Module2/test.py:38-66: build the model, load ``G_A``, run the
 generator over the dataset and write the frames.  ``--save_format npy`` (the default) writes ``fake_B`` as one ``.npy`` per
 frame; ``png`` writes every visual of ``get_current_visuals()`` as ``<stem>_<label>.png``, the names the reference's
-util/visualizer.py save_images gives, through the device sink of data/visuals.py; ``both`` does both.  The HTML page of the
-reference's visualizer is not written."""
+util/visualizer.py save_images gives, through the device sink of data/visuals.py; ``both`` does both.  ``--png_encoder device``
+(with ``png`` / ``both``) makes the PNG files on the device (apd_png_encode) instead of in PIL on the host: the same pixels in
+larger files.  The HTML page of the reference's visualizer is not written."""
 import os
 
 import numpy as np
@@ -13,10 +14,11 @@ from .models import create_model
 from .options.base_options import TestOptions
 
 SAVE_FORMATS = ('npy', 'png', 'both')
+PNG_ENCODERS = ('host', 'device')
 
 
 def parse(argv=None):
-    """TestOptions plus --save_format, which is this entry point's own flag"""
+    """TestOptions plus --save_format and --png_encoder, which are this entry point's own flags"""
     options = TestOptions()
     initialize = options.initialize
 
@@ -24,6 +26,9 @@ def parse(argv=None):
         p = initialize(p)
         p.add_argument('--save_format', type=str, default='npy', choices=SAVE_FORMATS,
                        help='npy: fake_B per frame as .npy; png: every visual as <stem>_<label>.png; both')
+        p.add_argument('--png_encoder', type=str, default='host', choices=PNG_ENCODERS,
+                       help='with --save_format png|both: host = PIL on a thread pool; device = the files are encoded on the GPU '
+                            '(fixed-Huffman deflate: same pixels, larger files) and the host only writes them')
         return p
     options.initialize = with_save_format
     return options.parse(argv)
@@ -59,7 +64,8 @@ def main(argv=None, prepare_model=None):
             from .data import visuals
             stems = [os.path.splitext(os.path.basename(path))[0] for path in paths]
             shown = {label: t for label, t in model.get_current_visuals().items() if torch.is_tensor(t) and t.dim() == 4}
-            visuals.save_png_batch(shown, {label: [os.path.join(out_dir, '%s_%s.png' % (s, label)) for s in stems] for label in shown})
+            visuals.save_png_batch(shown, {label: [os.path.join(out_dir, '%s_%s.png' % (s, label)) for s in stems] for label in shown},
+                                   encoder=opt.png_encoder)
         n += len(paths)
     print('wrote %d frames to %s' % (n, out_dir))
 

@@ -118,6 +118,37 @@ int apd_landmark_marks(const float* frames, const float* lm, const int32_t* win,
 int32_t apd_frames_to_u8_ok(const float* src, const uint8_t* dst, int32_t N, int32_t C, int32_t H, int32_t W);
 int apd_frames_to_u8(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, uint8_t* dst, void* stream);
 
+/* ---- PNG files encoded on the device: the opt-in sink of test.py / end2end.py (--png_encoder device).  Added as above:
+ * APD_ABI_VERSION stays 1. */
+
+#define APD_MAX_PNG_SIDE 2048  /* frame height / width */
+
+/* One complete PNG file per frame of src, device (N, C, H, W) float32: 8-bit samples, no interlace; channels 3 = colour
+ * type 2 with grey tiled to RGB, channels 1 = colour type 0 (needs C == 1).  The pixel bytes are apd_frames_to_u8's.
+ *   dst      N slots of slot_bytes each; frame n's file is dst[n slot_bytes .. n slot_bytes + sizes[n]): signature, IHDR, IDAT
+ *            chunks, IEND.  Bytes of a slot past sizes[n] are not written.
+ *   sizes    N int32
+ *   ws       device workspace of at least apd_png_workspace_bytes(N, H, W, channels) bytes, owned by the caller; its
+ *            contents mean nothing between calls
+ * dst and sizes are 4-byte aligned and each either device memory or pinned host memory mapped for the device (the rule of
+ * apd_frames_to_u8: pageable memory is refused).  The call enqueues two launches on `stream` and does not synchronise; no
+ * atomics touch the output, and the same input gives the same bytes.
+ * Stream: the frame is cut into bands of R = min(16, 16384 / (W channels + 1)) rows; a band is filtered on its own (first row
+ * Sub, the others Up against the image's row above) and is one fixed-Huffman deflate block -- literals and runs at distance
+ * 1 -- closed by an empty stored block, in an IDAT chunk of its own; a last 9-byte IDAT chunk ends the zlib stream with the
+ * Adler-32.  Any PNG decoder reads it; it is larger than what zlib's search would give.
+ * apd_png_bound: bytes of a slot that hold any frame of that shape, a multiple of 4, at most
+ *   9/8 H (W channels + 1) + 64 H + 256; -1 (with a message) outside the served region.
+ * Served: N 1..65535, C 1 or 3, channels 1 or 3 (1 only with C == 1), H, W 1..APD_MAX_PNG_SIDE, slot_bytes a multiple of 4
+ * and >= apd_png_bound, N slot_bytes < 2^31.  apd_png_encode_ok needs no device and checks everything but where the
+ * pointers live. */
+int64_t apd_png_bound(int32_t H, int32_t W, int32_t channels);
+int64_t apd_png_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t channels);
+int32_t apd_png_encode_ok(const float* src, const uint8_t* dst, const int32_t* sizes, const void* ws, int32_t N, int32_t C,
+                          int32_t H, int32_t W, int32_t channels, int64_t slot_bytes, int64_t ws_bytes);
+int apd_png_encode(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, int32_t channels, uint8_t* dst,
+                   int64_t slot_bytes, int32_t* sizes, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
