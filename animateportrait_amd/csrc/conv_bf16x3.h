@@ -21,7 +21,10 @@
 //     list.  The (tile, chunk) stages form one flat software pipeline -- stage g+2 is issued to the LDS-DMA
 //     while stage g multiplies, across tile boundaries -- so the first-stage latency of a tile and the drain of
 //     the previous tile's output stores hide under MFMA work; the one barrier per stage sits in front of the
-//     LAST tap of a stage (whose fragments are already in registers), so the matrix pipe never idles at it;
+//     LAST tap of a stage (whose fragments are already in registers), so the matrix pipe never idles at it.
+//     The issue window of stage g+2 is the last tap of stage g plus the first taps of stage g+1 (the buffer is free
+//     from stage g's barrier on; the pieces are awaited at stage g+1's): the split 3x3 stride-1 tiles spread the
+//     pieces over it, one per D MFMAs (bf3_dma_sched), the other families issue them all in the last tap of stage g;
 //   * epilogue identical to the fp32 kernel (bias, activation, InstanceNorm partial statistics).
 #pragma once
 #include <type_traits>
@@ -83,6 +86,9 @@ struct Bf3Cfg {
     static_assert(IH < 128 && IW < 256, "piece geometry is packed into 15 bits");
     // two workgroups share a CU when two stage pairs fit its 160 KB of LDS: the kernel is then compiled for <= 256 registers
     static constexpr int WG_PER_CU = (PARTS == 1 || 2 * (X_SLOTS + PARTS * TMAX * 2 * CO_TILE) * 16 + 1024 <= 80 * 1024) ? 2 : 1;
+    // the LDS-DMA pieces of a stage are spread over the following stage's taps (bf3_dma_sched): the split 3x3 stride-1 tiles
+    // (every other family keeps the whole issue in the stage's last tap: profiles/r07_dma_spread.md)
+    static constexpr bool DMA_SPREAD = K_ == 3 && S_ == 1 && !ROW_ && PARTS_ == 2;
     static int wfloats(int ntaps) { return 2 * ntaps * 2 * CO_TILE * 4; }   // floats per packed (cout tile, chunk) weight block: always both parts
     static size_t lds_bytes(int ntaps) {                                                          // two stages (+ patches)
         const size_t stage = (size_t)(X_SLOTS + w_slots(ntaps)) * 16, epi = (size_t)EPI_FLOATS * 4;
@@ -98,6 +104,28 @@ __device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
 struct Bf3Tile {
     int n, cot, ty, tx;
 };
+
+// Where the NPIECE LDS-DMA pieces of chunk c+2 are issued.  Their target, the buffer of stage c, is free from stage c's barrier
+// on, and they only have to have landed at the barrier of stage c+1: the window is the last tap of stage c (NM MFMA slots) plus
+// the taps of stage c+1 that leave two whole taps in front of that barrier.  D = the largest distance (in MFMA slots) at which
+// one piece per D slots still fits the window; piece j < N0 goes behind slot (j + 1) * D - 1 of the last tap of stage c, piece
+// N0 + t * PPT + k behind slot (k + 1) * D - 1 of tap t <= LAST_ISSUE_TAP of stage c+1.
+// D == 0: no window (fewer than four taps per stage, or not enabled) -- every piece in the last tap of stage c.
+struct Bf3DmaSched {
+    int D, LAST_ISSUE_TAP, PPT, N0;
+};
+constexpr Bf3DmaSched bf3_dma_sched(bool enabled, int npiece, int nm, int nreal) {
+    const int taps = nreal - 3;                                    // taps of stage c+1 that may carry pieces
+    if (enabled && taps >= 1)
+        for (int d = nm; d >= 1; --d) {
+            const int ppt = nm / d;
+            if ((taps + 1) * ppt >= npiece) {
+                const int n0 = ppt < npiece ? ppt : npiece;
+                return {d, (npiece - n0 + ppt - 1) / ppt - 1, ppt, n0};
+            }
+        }
+    return {0, -1, 0, npiece};
+}
 
 // LDS-DMA issued behind the compiler's back.  With the builtin, the compiler books every in-flight
 // global_load_lds as a "flat access that may touch LDS" and degrades each later s_waitcnt on an LDS read to
@@ -330,6 +358,15 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
         const DmaCtx d = dma_setup(t.n, t.cot, chunk_, buf);
         static_for<NPIECE>([&](auto jt) __attribute__((always_inline)) { dma_piece(d, goff, goff, false, jt); });
     };
+    // ---- the issue schedule (bf3_dma_sched) and the state a stage hands to the next one: the pieces N0 .. NPIECE-1 of the chunk
+    // it staged are issued during the next stage's taps 0 .. LAST_ISSUE_TAP, from the SAME pinned scalars and per-lane offsets
+    // (no select, no address arithmetic between those pieces and the MFMAs), under the same scalar flag.
+    constexpr int NM_STAGE = (PARTS == 2 ? 3 : 1) * MT * NT;       // MFMA slots of a tap
+    constexpr Bf3DmaSched SCHED = bf3_dma_sched(C::DMA_SPREAD, NPIECE, NM_STAGE, TMAX);
+    constexpr int DMA_D = SCHED.D, LAST_ISSUE_TAP = SCHED.LAST_ISSUE_TAP, DMA_PPT = SCHED.PPT, DMA_N0 = SCHED.N0;
+    DmaCtx pend;
+    int pig[NIT];
+    int pdma;
 
     // fragment addresses (16-byte slots)
     const int a_slot = half * CO_TILE + wco * MT * 32 + l32;                       // + ((part*T + t)*2) * CO_TILE + m*32
@@ -424,6 +461,15 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
     dma_wait_all();
     __syncthreads();
     AP_STAMP(8, 0);                                                // first two stages landed
+    // the launch's first two stages are staged whole: nothing pending.  (The carried scalars start from scalar registers, not
+    // from constants: a zero shared with a vector register's initial value turns the whole carried chain into vector registers,
+    // which the raw assembly of a piece cannot take.)
+    if constexpr (DMA_D > 0) {
+        pend = dma_setup(cur.n, cur.cot, 1, 1);
+        asm volatile("s_mov_b32 %0, 0" : "=s"(pdma));
+#pragma unroll
+        for (int k = 0; k < NIT; ++k) pig[k] = cgoff[k];
+    }
 
     // taps of the 2 x 2 window that exist for the current tile (fused sub-pixel phases; wave-uniform)
     auto tapmask_of = [&](const Bf3Tile& t) -> unsigned {
@@ -494,7 +540,55 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
                     else acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cb][m], xh, acc[m][q], 0, 0, 0);
                 };
                 constexpr int NM = (PARTS == 2 ? 3 : 1) * MT * NT, NRD = PARTS * (MT + NT);
-                if (!last) {
+                bool spread_tap = false;
+                if constexpr (DMA_D > 0) {
+                    static_assert(MASK == 0 && NM == NM_STAGE, "one issue schedule for every stage of the kernel");
+                    spread_tap = !last && ti <= LAST_ISSUE_TAP;
+                }
+                if (spread_tap) {
+                    if constexpr (DMA_D > 0) {
+                    // a tap that carries deferred LDS-DMA pieces of the PREVIOUS stage's refill (bf3_dma_sched).  The scalar branch
+                    // of a piece ends a scheduling region, so the order is written out slot by slot: the next tap's fragment
+                    // reads where the plain form below puts them (one in front of every PER-th MFMA), a piece behind every D-th MFMA.
+                    constexpr int NRD1 = PARTS * (MT + 1);
+                    const int kx2 = WIN ? (tp + 1) / KD : 0, ky2 = WIN ? (tp + 1) % KD : 0;
+                    const bool same_col = WIN && kx2 == kx;         // (windowed form: one new window row instead of NT)
+                    const int nrd = same_col ? NRD1 : NRD;
+                    const int per = (NM + nrd - 1) / nrd;
+                    const int tn = WIN ? ky2 * K + kx2 : t + 1;      // the next tap's index in the weight image
+                    auto read_next = [&](int r) __attribute__((always_inline)) {
+                        if constexpr (WIN) {
+                            if (r < PARTS * MT) {
+                                const uint4* Wc = wbuf + P * STAGE + a_slot + ((((PARTS == 2 && (r & 1)) ? 1 : 0) * T + tn) * 2) * CO_TILE + (r / PARTS) * 32;
+                                if (PARTS == 2 && (r & 1)) al[cb ^ 1][r / PARTS] = *reinterpret_cast<const bf16x8*>(Wc);
+                                else ah[cb ^ 1][r / PARTS] = *reinterpret_cast<const bf16x8*>(Wc);
+                            } else {
+                                const int q = (r - PARTS * MT) / PARTS;
+                                const int row = same_col ? ky2 + NT - 1 : q, col = same_col ? kx : kx2, wsel = same_col ? wb : wb ^ 1;
+                                const uint4* Xc = xbuf + P * STAGE + b_slot + row * IW + col;
+                                if (PARTS == 2 && (r & 1)) wl[wsel][row] = *reinterpret_cast<const bf16x8*>(Xc + XP);
+                                else wh[wsel][row] = *reinterpret_cast<const bf16x8*>(Xc);
+                            }
+                        } else {
+                            fetch_one(P, tn, cb ^ 1, r);
+                        }
+                    };
+                    static_for<NM>([&](auto it) __attribute__((always_inline)) {
+                        constexpr int i = decltype(it)::value;
+                        if (i % per == 0 && i / per < nrd) read_next(i / per);
+                        mfma_one(i);
+                        if constexpr (i % DMA_D == DMA_D - 1 && i / DMA_D < DMA_PPT) {
+                            static_for<LAST_ISSUE_TAP + 1>([&](auto tt) __attribute__((always_inline)) {
+                                constexpr int j = DMA_N0 + decltype(tt)::value * DMA_PPT + i / DMA_D;
+                                if constexpr (j < NPIECE) {
+                                    if (ti == decltype(tt)::value && pdma) dma_piece(pend, pig, pig, false, std::integral_constant<int, j>{});
+                                }
+                            });
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                    }
+                } else if (!last) {
                     int nrd = NRD;                                  // LDS reads issued for the next tap
                     if constexpr (WIN) {
                         const int kx2 = (tp + 1) / KD, ky2 = (tp + 1) % KD;
@@ -565,12 +659,19 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
                     static_for<NM>([&](auto it) __attribute__((always_inline)) {
                         constexpr int i = decltype(it)::value;
                         if (real_tap) mfma_one(i);
-                        static_for<PPS>([&](auto ppt) __attribute__((always_inline)) {
-                            constexpr int j = i * PPS + decltype(ppt)::value;
-                            if constexpr (j < NPIECE) {
-                                if (dma) dma_piece(d, ig, ig, false, std::integral_constant<int, j>{});
+                        if constexpr (DMA_D > 0) {
+                            // the first N0 pieces, one behind every D-th MFMA; the others ride on the next stage's taps
+                            if constexpr (i % DMA_D == DMA_D - 1 && i / DMA_D < DMA_N0) {
+                                if (dma) dma_piece(d, ig, ig, false, std::integral_constant<int, i / DMA_D>{});
                             }
-                        });
+                        } else {
+                            static_for<PPS>([&](auto ppt) __attribute__((always_inline)) {
+                                constexpr int j = i * PPS + decltype(ppt)::value;
+                                if constexpr (j < NPIECE) {
+                                    if (dma) dma_piece(d, ig, ig, false, std::integral_constant<int, j>{});
+                                }
+                            });
+                        }
                         if constexpr (XPF && i >= R0) {
                             if (more) {
 #pragma unroll
@@ -583,6 +684,12 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     });
+                    if constexpr (DMA_D > 0) {                     // the rest of this refill: the next stage's first taps
+                        pend = d;
+                        pdma = dma;
+#pragma unroll
+                        for (int k = 0; k < NIT; ++k) pig[k] = ig[k];
+                    }
                 }
             }
         };
@@ -1023,7 +1130,17 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
         if (!has_next) break;
         __syncthreads();                                           // patches and statistics consumed: refill that stage
         AP_STAMP(5, 0);
-        if (!AP_ABLATE(p, 1)) issue(nxt, ngoff, 1, pl);
+        if constexpr (DMA_D > 0) {
+            // the next tile's chunk 1 is "the refill of stage -1": its first N0 pieces here, the others on the taps of the
+            // next tile's stage 0, like every other refill (stage_sync(0) awaits them; stage 1 reads them)
+            pend = dma_setup(nxt.n, nxt.cot, 1, pl);
+            pdma = __builtin_amdgcn_readfirstlane(AP_ABLATE(p, 1) ? 0 : 1);
+#pragma unroll
+            for (int k = 0; k < NIT; ++k) pig[k] = ngoff[k];
+            static_for<DMA_N0>([&](auto jt) __attribute__((always_inline)) {
+                if (pdma) dma_piece(pend, pig, pig, false, jt);
+            });
+        } else if (!AP_ABLATE(p, 1)) issue(nxt, ngoff, 1, pl);
         AP_STAMP(6, 0);                                            // the next tile's chunk 1 is on its way
 #ifdef APAMD_ABLATION
         ++stamp_tile;
