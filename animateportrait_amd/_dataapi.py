@@ -48,6 +48,15 @@ SIGNATURES.update({
 })
 MAX_PNG_SIDE = 2048
 
+# the device JPEG encoder (csrc/data/jpeg_encode.hip), added the same way
+SIGNATURES.update({
+    'apd_jpeg_bound': (_i64, [_i32] * 3),
+    'apd_jpeg_workspace_bytes': (_i64, [_i32] * 4),
+    'apd_jpeg_encode_ok': (ctypes.c_int32, [_ptr] * 4 + [_i32] * 6 + [_i64] * 2),
+    'apd_jpeg_encode': (ctypes.c_int, [_ptr] + [_i32] * 6 + [_ptr, _i64, _ptr, _ptr, _i64, _ptr]),
+})
+MAX_JPEG_SIDE = 2048
+
 _lib = None
 _lock = threading.Lock()
 

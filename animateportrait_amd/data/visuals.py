@@ -6,7 +6,9 @@
     pinned host buffer the kernel writes directly,
   * ``save_png_batch`` the sink: one launch per visual, one stream synchronisation, PNG encoding on a thread pool,
   * ``encode_png_batch`` complete PNG files made on the device (apd_png_encode); ``save_png_batch(encoder='device')`` writes
-    them, and the pool is left with the write() calls.
+    them, and the pool is left with the write() calls,
+  * ``encode_jpeg_batch`` complete baseline JPEG files made on the device (apd_jpeg_encode): the frames of the MJPEG clip
+    ``end2end.py --video avi`` writes through util/avi.py.
 
 A missing library or a refused call raises; nothing here falls back to the host."""
 import concurrent.futures
@@ -146,6 +148,31 @@ def encode_png_batch(frames, channels=3, slot=0):
     with torch.cuda.device(frames.device):
         D.check(lib.apd_png_encode(_p(frames), n, c, h, w, int(channels), _p(buf), buf.shape[1], _p(sizes), _p(ws), ws.numel(),
                                    _stream(frames.device)), 'png_encode')
+    return buf, sizes
+
+
+_JPEG = {}        # (N, C, H, W, channels, device, slot) -> (pinned file slots, pinned sizes, device workspace), reused
+
+
+def encode_jpeg_batch(frames, channels=3, quality=90, slot=0):
+    """frames (N, C, H, W) device float32, C in {1, 3} -> (buf (N, apd_jpeg_bound) uint8, sizes (N,) int32), both pinned host
+    buffers of this (shape, channels, device, slot) that the kernels write themselves: after the stream has been synchronised,
+    frame i's complete baseline JPEG file is ``buf[i, :sizes[i]]``.  channels 3: Y Cb Cr 4:4:4, grey tiled; channels 1:
+    greyscale, C must be 1.  quality 1..100 scales the standard tables as PIL's ``quality`` does."""
+    frames = _device_f32(frames, 'encode_jpeg_batch', 4)
+    n, c, h, w = frames.shape
+    lib = D.lib()
+    key = (n, c, h, w, int(channels), str(frames.device), slot)
+    if key not in _JPEG:
+        bound, ws = lib.apd_jpeg_bound(h, w, int(channels)), lib.apd_jpeg_workspace_bytes(n, h, w, int(channels))
+        if bound < 0 or ws < 0:
+            raise RuntimeError('libapdata jpeg_encode refused: %s' % D.last_error())
+        _JPEG[key] = (torch.empty((n, bound), dtype=torch.uint8).pin_memory(), torch.zeros((n,), dtype=torch.int32).pin_memory(),
+                      torch.empty((ws,), dtype=torch.uint8, device=frames.device))
+    buf, sizes, ws = _JPEG[key]
+    with torch.cuda.device(frames.device):
+        D.check(lib.apd_jpeg_encode(_p(frames), n, c, h, w, int(channels), int(quality), _p(buf), buf.shape[1], _p(sizes), _p(ws),
+                                    ws.numel(), _stream(frames.device)), 'jpeg_encode')
     return buf, sizes
 
 

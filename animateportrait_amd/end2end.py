@@ -4,7 +4,8 @@ main_end2end_module2.py:90-124, 294-343.
 The reference writes one landmark txt + one landmark PNG per frame, shells out to ``python test.py --model
 geomcgt_ifw_test`` (which re-reads them, builds the motion grids with scipy on the CPU and runs the model at batch 1),
 copies the PNGs it wrote and calls ffmpeg at 62.5 fps.  Here: photo + a landmark clip in, frames (and the video, when
-ffmpeg exists) out, through ``stream.ClipStreamer`` in batches.
+ffmpeg exists) out, through ``stream.ClipStreamer`` in batches.  ``--video avi`` needs no ffmpeg: the frames are encoded as
+JPEG on the GPU and muxed with the sound into ``<out>/output.avi`` here (util/avi.py); ``--frames none`` then skips the PNGs.
 
     python -m animateportrait_amd.end2end --photo face.png --landmarks Data/Alm_txt/MTCNN/<db>_MTCNN \\
         --landmark_scale 0.5 --name formal/drawing --epoch 70 --out output/<db> [--audio a.wav]
@@ -120,7 +121,48 @@ def make_parser():
                          'of --batch (the same pixels in larger files; the host only writes them)')
     ap.add_argument('--png_channels', type=int, choices=(1, 3), default=3,
                     help='with --png_encoder device: 3 = RGB files as the host writes them, 1 = greyscale files (1-channel frames only)')
+    ap.add_argument('--video', choices=('ffmpeg', 'avi'), default='ffmpeg',
+                    help='ffmpeg: assemble the frame PNGs with an ffmpeg binary when one is found (output.mp4).  avi: encode the '
+                         'frames as baseline JPEG on the GPU (apd_jpeg_encode) and write <out>/output.avi -- MJPG video with the PCM '
+                         'sound of --audio / --wav -- in this process; no external tool is used')
+    ap.add_argument('--video_quality', type=int, default=90, help='with --video avi: JPEG quality 1..100 (the IJG scale PIL uses)')
+    ap.add_argument('--video_channels', type=int, choices=(1, 3), default=None,
+                    help='with --video avi: 1 = greyscale JPEG (1-channel frames only), 3 = Y Cb Cr 4:4:4; default: 1 for 1-channel '
+                         'frames, otherwise 3')
+    ap.add_argument('--frames', choices=('png', 'none'), default='png',
+                    help='none: write no per-frame PNG (only with --video avi)')
     return ap
+
+
+def write_avi(frames, path, fps, audio=None, batch=16, channels=None, quality=90):
+    """frames (T, C, H, W) -> an AVI file of MJPG frames (util/avi.py) with the PCM sound of the wav `audio`.  The frames are
+    encoded where they are, --batch at a time (data/visuals.encode_jpeg_batch), into two pinned buffers in turn, and a writer
+    thread appends a batch to the file while the next is encoded: the pattern of write_frames."""
+    import concurrent.futures
+    from .data import visuals
+    from .util import avi
+    if not frames.is_cuda:
+        frames = frames.cuda()
+    if channels is None:
+        channels = 1 if frames.shape[1] == 1 else 3
+    num, den = avi.fps_fraction(fps)
+    writer = avi.AviWriter(path, frames.shape[3], frames.shape[2], num, den, audio=audio)
+    pending = None
+    with concurrent.futures.ThreadPoolExecutor(max_workers=1) as pool:
+        try:
+            for turn, k0 in enumerate(range(0, frames.shape[0], batch)):
+                buf, sizes = visuals.encode_jpeg_batch(frames[k0:k0 + batch], channels=channels, quality=quality, slot='clip%d' % (turn & 1))
+                done = torch.cuda.Event()
+                done.record()
+                if pending is not None:
+                    pending.result()          # the other buffer is in the file before it is encoded into again (next turn)
+                done.synchronize()
+                pending = pool.submit(writer.add_frames, buf, sizes)
+            if pending is not None:
+                pending.result()
+        finally:
+            writer.close()
+    return writer.frames
 
 
 def write_frames(frames, fdir, encoder='host', batch=16, channels=3):
@@ -153,7 +195,9 @@ def write_frames(frames, fdir, encoder='host', batch=16, channels=3):
         list(pending)
 
 
-def main(argv=None):
+def main(argv=None, prepare_model=None):
+    """``prepare_model(model)`` runs after the model is built and before setup(), as in test.main: the place to attach the frozen
+    third-party networks (aux['netF'], aux['modnet'])."""
     ap = make_parser()
     a, rest = ap.parse_known_args(argv)
     if sum(x is not None for x in (a.landmarks, a.landmarks_npy, a.wav)) != 1:
@@ -163,6 +207,10 @@ def main(argv=None):
     if a.wav is not None and a.speaker_emb is None:
         ap.error('--wav needs --speaker_emb (the 256-d resemblyzer embedding the speaker-aware branch is conditioned on, '
                  'main_end2end_module2.py:215-217); a zero vector is not a neutral default')
+    if a.frames == 'none' and a.video != 'avi':
+        ap.error('--frames none leaves nothing to assemble: it needs --video avi')
+    if not 1 <= a.video_quality <= 100:
+        ap.error('--video_quality %d, served: 1 .. 100' % a.video_quality)
     if a.wav is not None and not a.no_autovc and not os.path.exists(a.load_AUTOVC_name):
         ap.error('--wav: AutoVC checkpoint %s not found; the reference converts the spectrogram before Module1 '
                  '(pass --load_AUTOVC_name, or --no_autovc to feed the raw mel on purpose)' % a.load_AUTOVC_name)
@@ -172,6 +220,8 @@ def main(argv=None):
     opt = TestOptions().parse(defaults + rest)
     torch.cuda.set_device(opt.gpu_ids[0])
     model = create_model(opt)
+    if prepare_model is not None:
+        prepare_model(model)
     model.setup(opt)                    # '<epoch>_net_G_A.pth' + the static drawing generator; missing files are errors
     model.eval()
     if a.wav is not None:
@@ -189,9 +239,16 @@ def main(argv=None):
         raise SystemExit('no matting network is attached (aux["modnet"]): pass --matte PNG')
     frames = stream.ClipStreamer(model, batch=a.batch, triangulate=a.triangulate).run(photo, lm0, seq, matte=matte)
     fdir = os.path.join(a.out, 'frames')
-    os.makedirs(fdir, exist_ok=True)
-    write_frames(frames, fdir, a.png_encoder, a.batch, a.png_channels)
-    print('wrote %d frames to %s' % (frames.shape[0], fdir))
+    if a.frames == 'png':
+        os.makedirs(fdir, exist_ok=True)
+        write_frames(frames, fdir, a.png_encoder, a.batch, a.png_channels)
+        print('wrote %d frames to %s' % (frames.shape[0], fdir))
+    if a.video == 'avi':
+        os.makedirs(a.out, exist_ok=True)
+        video = os.path.join(a.out, 'output.avi')
+        write_avi(frames, video, a.fps, a.audio, a.batch, a.video_channels, a.video_quality)
+        print('output is', video)
+        return 0
     ffmpeg = shutil.which('ffmpeg')
     if ffmpeg is None:
         print('ffmpeg not found: frames only (the reference assembles them at %.1f fps, :118-121)' % a.fps)

@@ -149,6 +149,50 @@ int32_t apd_png_encode_ok(const float* src, const uint8_t* dst, const int32_t* s
 int apd_png_encode(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, int32_t channels, uint8_t* dst,
                    int64_t slot_bytes, int32_t* sizes, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- baseline JPEG files encoded on the device: the frames of an MJPEG clip (end2end.py --video avi, util/avi.py).  Added
+ * as above: APD_ABI_VERSION stays 1. */
+
+#define APD_MAX_JPEG_SIDE 2048  /* frame height / width */
+
+/* One complete baseline JPEG file per frame of src, device (N, C, H, W) float32.  The sample bytes are apd_frames_to_u8's.
+ * channels 1 (needs C == 1): one component.  channels 3: Y Cb Cr, every component sampled 1x1 (4:4:4), grey tiled to RGB
+ * first when C == 1.
+ *   dst      N slots of slot_bytes each; frame n's file is dst[n slot_bytes .. n slot_bytes + sizes[n]).  Bytes of a slot past
+ *            sizes[n] are not written.
+ *   sizes    N int32
+ *   quality  1..100: the tables of ITU T.81 Annex K.1 / K.2 scaled by the IJG rule, s = quality < 50 ? 5000 / quality :
+ *            200 - 2 quality, t = clamp((base s + 50) / 100, 1, 255) -- the tables PIL's save(quality=) writes
+ *   ws       device workspace of at least apd_jpeg_workspace_bytes(N, H, W, channels) bytes, owned by the caller; its
+ *            contents mean nothing between calls
+ * dst and sizes are 4-byte aligned and each either device memory or pinned host memory mapped for the device (the rule of
+ * apd_frames_to_u8: pageable memory is refused).  The call enqueues three launches on `stream`, starts no stream of its own
+ * and does not synchronise; no atomics touch global memory, and the same input gives the same bytes.
+ * File: SOI, JFIF APP0, DQT (one table for channels 1, two for 3), SOF0 (8 bit, the true H and W), DHT (always the four
+ * tables of Annex K.3), DRI, SOS, the scan, EOI at sizes[n] - 2.  Edges are padded to a multiple of 8 by replicating the
+ * last column / row.  The restart interval is ceil(W / 8) MCUs, one MCU row: every row is a byte-aligned segment with its
+ * DC prediction reset, padded with 1-bits and followed by RSTm (m = row mod 8) unless it is the last; a segment is encoded
+ * by one workgroup, independently of every other.
+ * Arithmetic, integers only (csrc/data/jpeg_core.h; a host build gives the same bytes):
+ *   colour    Y = (19595 R + 38470 G + 7471 B + 2^15) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 128 2^16 + 2^15 - 1) >> 16,
+ *             Cr = (32768 R - 27439 G - 5329 B + 128 2^16 + 2^15 - 1) >> 16: the JFIF matrix at 16 fractional bits; grey
+ *             gives Cb = Cr = 128 exactly
+ *   DCT       separable, on samples - 128, cosines C(u) / 2 cos((2 x + 1) u pi / 16) rounded to 20 fractional bits: the row
+ *             pass in int32, kept whole; the column pass accumulated in int64 and rounded half up to 20 fractional bits
+ *             (an int32); the DC term is not taken from the passes, it is the sum of the samples / 8 exactly
+ *   quantise  sign(v) ((|v| + q 2^19) / (q 2^20)): round half away from zero; AC levels clamped to +-1023
+ * apd_jpeg_bound: bytes of a slot that hold any frame of that shape, a multiple of 4: a symbol is at most 26 bits, a block
+ * 64 symbols = 208 bytes, 416 once every byte is stuffed, so header (613 bytes at most) + ceil(H / 8) (416 blocks per row
+ * + 2) + 2, rounded up; -1 (with a message) outside the served region.
+ * Served: N 1..65535, C 1 or 3, channels 1 or 3 (1 only with C == 1), H, W 1..APD_MAX_JPEG_SIDE, quality 1..100, slot_bytes
+ * a multiple of 4 and >= apd_jpeg_bound, N slot_bytes < 2^31.  apd_jpeg_encode_ok needs no device and checks everything but
+ * where the pointers live. */
+int64_t apd_jpeg_bound(int32_t H, int32_t W, int32_t channels);
+int64_t apd_jpeg_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t channels);
+int32_t apd_jpeg_encode_ok(const float* src, const uint8_t* dst, const int32_t* sizes, const void* ws, int32_t N, int32_t C,
+                           int32_t H, int32_t W, int32_t channels, int32_t quality, int64_t slot_bytes, int64_t ws_bytes);
+int apd_jpeg_encode(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, int32_t channels, int32_t quality,
+                    uint8_t* dst, int64_t slot_bytes, int32_t* sizes, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
