@@ -154,6 +154,7 @@ SIGNATURES = {
     'ap_instnorm_bwd': (ctypes.c_int, [c_f32p, ctypes.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p,
                                        ctypes.c_void_p]),
+    'ap_instnorm_bwd_route': (ctypes.c_int, [ctypes.c_int32] * 5 + [ctypes.c_char_p, ctypes.c_int32]),
     'ap_instnorm_bwd_split_ok': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     'ap_instnorm_bwd_split': (ctypes.c_int, [c_f32p, ctypes.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_int32,
                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
@@ -165,6 +166,7 @@ SIGNATURES = {
     'ap_conv2d_wgrad_xs': (ctypes.c_int, [ctypes.POINTER(ApWgradDesc), ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p]),
     'ap_act_bwd': (ctypes.c_int, [c_f32p, ctypes.c_int32, c_f32p, c_f32p, ctypes.c_int32, ctypes.c_int32,
                                   ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_void_p]),
+    'ap_act_bwd_route': (ctypes.c_int, [ctypes.c_int32] * 3 + [ctypes.c_char_p, ctypes.c_int32]),
     'ap_bias_grad': (ctypes.c_int, [c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_void_p]),
     'ap_bias_grad_workspace_floats': (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     'ap_bias_grad_ws': (ctypes.c_int, [c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p,

@@ -12,6 +12,7 @@
 #include "common.h"
 #include <type_traits>
 
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -117,6 +118,11 @@ __device__ __forceinline__ float act_grad_from_xhat(float xh, int act) {
     if (act == 2) return xh > 0.f ? 1.f : 0.2f;
     return 1.f;
 }
+
+// tanh'(pre) = 1 - out^2 as ONE fused operation, spelled out.  Left to the compiler's contraction, the 16-byte path of
+// act_bwd_kernel<true> came out as multiply + subtract and every other form as a fused multiply-add, so ap_act_bwd_bias and
+// ap_act_bwd disagreed in the last bit of dy on the generator's tanh layer.
+__device__ __forceinline__ float tanh_grad(float o) { return __builtin_fmaf(-o, o, 1.f); }
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
 #pragma unroll
@@ -902,8 +908,8 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
                     gv.x = ov.x > 0.f ? gv.x : 0.2f * gv.x; gv.y = ov.y > 0.f ? gv.y : 0.2f * gv.y;
                     gv.z = ov.z > 0.f ? gv.z : 0.2f * gv.z; gv.w = ov.w > 0.f ? gv.w : 0.2f * gv.w;
                 } else if (act == 3) {
-                    gv.x *= 1.f - ov.x * ov.x; gv.y *= 1.f - ov.y * ov.y;
-                    gv.z *= 1.f - ov.z * ov.z; gv.w *= 1.f - ov.w * ov.w;
+                    gv.x *= tanh_grad(ov.x); gv.y *= tanh_grad(ov.y);
+                    gv.z *= tanh_grad(ov.z); gv.w *= tanh_grad(ov.w);
                 }
             }
             reinterpret_cast<float4*>(out)[i] = gv;
@@ -932,7 +938,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
                 float v = g[k];
                 if (act == 1) v = o[k] > 0.f ? v : 0.f;
                 else if (act == 2) v = o[k] > 0.f ? v : 0.2f * v;
-                else if (act == 3) v *= 1.f - o[k] * o[k];
+                else if (act == 3) v *= tanh_grad(o[k]);
                 out[i] = v;
                 if constexpr (SUMS) ssum += v;
             }
@@ -985,7 +991,7 @@ __global__ __launch_bounds__(256) void act_bwd_fold1_kernel(const float* __restr
                 gv.x = o.x > 0.f ? gv.x : 0.2f * gv.x; gv.y = o.y > 0.f ? gv.y : 0.2f * gv.y;
                 gv.z = o.z > 0.f ? gv.z : 0.2f * gv.z; gv.w = o.w > 0.f ? gv.w : 0.2f * gv.w;
             } else if (act == 3) {
-                gv.x *= 1.f - o.x * o.x; gv.y *= 1.f - o.y * o.y; gv.z *= 1.f - o.z * o.z; gv.w *= 1.f - o.w * o.w;
+                gv.x *= tanh_grad(o.x); gv.y *= tanh_grad(o.y); gv.z *= tanh_grad(o.z); gv.w *= tanh_grad(o.w);
             }
             out[i] = gv;
         }
@@ -1044,9 +1050,62 @@ __global__ __launch_bounds__(64) void bias_sums_final_kernel(const float* __rest
 
 using namespace apamd;
 
+static int fold_pad_ok(int p1, int H, int W, const char* who) {
+    if (p1 < 0 || (p1 > 0 && (p1 >= H || p1 >= W))) return fail(AP_ERR_INVALID, "%s: fold pad %d vs %dx%d", who, p1, H, W);
+    return AP_OK;
+}
+
 static int fold_args_ok(const float* g1, int p1, int H, int W, const char* who) {
     if (!g1) return fail(AP_ERR_INVALID, "%s: null gradient", who);
-    if (p1 < 0 || (p1 > 0 && (p1 >= H || p1 >= W))) return fail(AP_ERR_INVALID, "%s: fold pad %d vs %dx%d", who, p1, H, W);
+    return fold_pad_ok(p1, H, W, who);
+}
+
+// Which kernel ap_instnorm_bwd launches for a plane geometry: the one place that decides it (the launcher switches on the answer,
+// ap_instnorm_bwd_route names it).  The forms with a `g2` template parameter (small, vec, fold1) are further split by the presence
+// of a second gradient at the launch.
+enum InBwdRoute {
+    INBWD_SMALL,            // instnorm_bwd_fused_small_kernel: unfolded, H W <= 1024 and not a multiple of 4
+    INBWD_VEC_256,          // instnorm_bwd_fused_vec_kernel<256>: unfolded, H W % 4 == 0, H W <= 4096
+    INBWD_VEC_1024,         //                              <1024>: ... H W <= 16384
+    INBWD_FOLD1_256,        // instnorm_bwd_fused_fold1_kernel<256>: pad-1 fold, W % 4 == 0, W >= 8, H >= 3
+    INBWD_FOLD1_1024,
+    INBWD_GENERAL_256,      // instnorm_bwd_fused_kernel<256>: everything else up to 4096 pixels
+    INBWD_GENERAL_1024,     //                          <1024>: ... up to 16384
+    INBWD_BIG,              // instnorm_bwd_fused_big_kernel<false>: 16384 < H W <= 65536, W % 4 == 0, unfolded
+    INBWD_BIG_FOLD,         //                              <true>: ... any fold
+    INBWD_BIG_BF16,         //                              <false, true>: unfolded, dy stored as bf16
+    INBWD_REDUCE_APPLY,     // the reduce / apply pair: all other planes
+};
+
+// act_bits: the launcher's `act` argument (activation in the low byte, bit 8 = dy stored as bf16)
+static int instnorm_bwd_route(int g1_pad, int act_bits, int H, int W, InBwdRoute* route) {
+    int rc = fold_pad_ok(g1_pad, H, W, "instnorm_bwd");
+    if (rc) return rc;
+    const bool ob16 = (act_bits & 0x100) != 0;  // bit 8: dy is stored as bf16 values (256 x 256-class planes without a fold only)
+    const int act = act_bits & 0xff;
+    if (act < 0 || act > 2) return fail(AP_ERR_INVALID, "instnorm_bwd: act %d", act);
+    if (ob16 && !(g1_pad == 0 && H * W > 16384 && H * W <= 65536 && (W % 4) == 0))
+        return fail(AP_ERR_UNSUPPORTED, "instnorm_bwd: a bf16 dy is written by the big-plane kernel only (%dx%d, fold %d)", H, W, g1_pad);
+    const bool plain_vec = g1_pad == 0 && ((H * W) & 3) == 0;     // unfolded gradient, whole 16-byte groups: the load-phase form
+    const bool fold1_vec = g1_pad == 1 && (W & 3) == 0 && H >= 3 && W >= 8;   // pad-1 fold, the same
+    if (g1_pad == 0 && H * W <= 1024 && ((H * W) & 3) != 0) *route = INBWD_SMALL;      // small planes that are not whole 16-byte groups
+    else if (H * W <= 4096) *route = plain_vec ? INBWD_VEC_256 : (fold1_vec ? INBWD_FOLD1_256 : INBWD_GENERAL_256);
+    else if (H * W <= 16384) *route = plain_vec ? INBWD_VEC_1024 : (fold1_vec ? INBWD_FOLD1_1024 : INBWD_GENERAL_1024);
+    else if (H * W <= 65536 && (W % 4) == 0 && W >= 4) *route = ob16 ? INBWD_BIG_BF16 : (g1_pad == 0 ? INBWD_BIG : INBWD_BIG_FOLD);
+    else *route = INBWD_REDUCE_APPLY;
+    return AP_OK;
+}
+
+// ... and ap_act_bwd's
+enum ActBwdRoute {
+    ACTBWD_FOLD1,           // act_bwd_fold1_kernel: pad-1 fold, W % 4 == 0, H >= 3
+    ACTBWD_GENERIC,         // act_bwd_kernel: 16-byte lanes for an unfolded gradient with H W % 4 == 0, else element-wise with FoldReader
+};
+
+static int act_bwd_route(int g1_pad, int H, int W, ActBwdRoute* route) {
+    int rc = fold_pad_ok(g1_pad, H, W, "act_bwd");
+    if (rc) return rc;
+    *route = g1_pad == 1 && (W & 3) == 0 && H >= 3 && W >= 4 ? ACTBWD_FOLD1 : ACTBWD_GENERIC;
     return AP_OK;
 }
 
@@ -1072,25 +1131,29 @@ int ap_instnorm_bwd(const float* g1, int32_t g1_pad, const float* g2, const floa
     int rc = fold_args_ok(g1, g1_pad, H, W, "instnorm_bwd");
     if (rc) return rc;
     if (!y || !mean || !rstd || !sums_ws || !dy) return fail(AP_ERR_INVALID, "instnorm_bwd: null pointer");
-    const bool ob16 = (act & 0x100) != 0;       // bit 8: dy is stored as bf16 values (256 x 256-class planes without a fold only)
+    InBwdRoute route;
+    rc = instnorm_bwd_route(g1_pad, act, H, W, &route);
+    if (rc) return rc;
     act &= 0xff;
-    if (act < 0 || act > 2) return fail(AP_ERR_INVALID, "instnorm_bwd: act %d", act);
     if (NC < 1 || NC > 65535) return fail(AP_ERR_UNSUPPORTED, "instnorm_bwd: N*C=%d", NC);
-    if (ob16 && !(g1_pad == 0 && H * W > 16384 && H * W <= 65536 && (W % 4) == 0))
-        return fail(AP_ERR_UNSUPPORTED, "instnorm_bwd: a bf16 dy is written by the big-plane kernel only (%dx%d, fold %d)", H, W, g1_pad);
-    const bool plain_vec = g1_pad == 0 && ((H * W) & 3) == 0;     // unfolded gradient, whole 16-byte groups: the load-phase form
-    const bool fold1_vec = g1_pad == 1 && (W & 3) == 0 && H >= 3 && W >= 8;   // pad-1 fold, the same
-    if (g1_pad == 0 && H * W <= 1024 && ((H * W) & 3) != 0) {      // small planes that are not whole 16-byte groups
+    switch (route) {
+    case INBWD_SMALL:
         if (g2) hipLaunchKernelGGL(instnorm_bwd_fused_small_kernel<true>, dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H * W, dy);
         else hipLaunchKernelGGL(instnorm_bwd_fused_small_kernel<false>, dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g2, y, mean, rstd, act, H * W, dy);
         return check_launch("instnorm_bwd_fused_small_kernel");
-    }
-    if (H * W <= 16384) {
-        if (H * W <= 4096) launch_instnorm_bwd_fused<256>(plain_vec, fold1_vec, g1, g1_pad, g2, y, mean, rstd, act, NC, H, W, dy, stream);
-        else launch_instnorm_bwd_fused<1024>(plain_vec, fold1_vec, g1, g1_pad, g2, y, mean, rstd, act, NC, H, W, dy, stream);
+    case INBWD_VEC_256:
+    case INBWD_FOLD1_256:
+    case INBWD_GENERAL_256:
+        launch_instnorm_bwd_fused<256>(route == INBWD_VEC_256, route == INBWD_FOLD1_256, g1, g1_pad, g2, y, mean, rstd, act, NC, H, W, dy, stream);
         return check_launch("instnorm_bwd_fused_kernel");
-    }
-    if (H * W <= 65536 && (W % 4) == 0 && W >= 4) {
+    case INBWD_VEC_1024:
+    case INBWD_FOLD1_1024:
+    case INBWD_GENERAL_1024:
+        launch_instnorm_bwd_fused<1024>(route == INBWD_VEC_1024, route == INBWD_FOLD1_1024, g1, g1_pad, g2, y, mean, rstd, act, NC, H, W, dy, stream);
+        return check_launch("instnorm_bwd_fused_kernel");
+    case INBWD_BIG:
+    case INBWD_BIG_FOLD:
+    case INBWD_BIG_BF16: {
         const size_t lds = 8 * 1024 * sizeof(float4);
         for (const void* fn : {reinterpret_cast<const void*>(&instnorm_bwd_fused_big_kernel<false>),
                                reinterpret_cast<const void*>(&instnorm_bwd_fused_big_kernel<true>),
@@ -1098,16 +1161,19 @@ int ap_instnorm_bwd(const float* g1, int32_t g1_pad, const float* g2, const floa
             rc = ensure_dyn_lds(fn, (int)lds);
             if (rc) return rc;
         }
-        if (ob16)
+        if (route == INBWD_BIG_BF16)
             hipLaunchKernelGGL((instnorm_bwd_fused_big_kernel<false, true>), dim3(NC), dim3(1024), lds, (hipStream_t)stream, g1, g1_pad,
                                g2, y, mean, rstd, act, H, W, dy);
-        else if (g1_pad == 0)
+        else if (route == INBWD_BIG)
             hipLaunchKernelGGL(instnorm_bwd_fused_big_kernel<false>, dim3(NC), dim3(1024), lds, (hipStream_t)stream, g1, g1_pad,
                                g2, y, mean, rstd, act, H, W, dy);
         else
             hipLaunchKernelGGL(instnorm_bwd_fused_big_kernel<true>, dim3(NC), dim3(1024), lds, (hipStream_t)stream, g1, g1_pad,
                                g2, y, mean, rstd, act, H, W, dy);
         return check_launch("instnorm_bwd_fused_big_kernel");
+    }
+    case INBWD_REDUCE_APPLY:
+        break;
     }
     hipLaunchKernelGGL(instnorm_bwd_reduce_kernel, dim3(NC), dim3(256), 0, (hipStream_t)stream, g1, g1_pad, g2, y,
                        mean, rstd, act, H, W, sums_ws);
@@ -1118,6 +1184,28 @@ int ap_instnorm_bwd(const float* g1, int32_t g1_pad, const float* g2, const floa
     hipLaunchKernelGGL(instnorm_bwd_apply_kernel, dim3(bx, NC), dim3(256), 0, (hipStream_t)stream, g1, g1_pad, g2, y,
                        mean, rstd, act, H, W, sums_ws, dy);
     return check_launch("instnorm_bwd_apply_kernel");
+}
+
+int ap_instnorm_bwd_route(int32_t g1_pad, int32_t has_g2, int32_t act_bits, int32_t H, int32_t W, char* buf, int32_t buflen) {
+    InBwdRoute route;
+    int rc = instnorm_bwd_route(g1_pad, act_bits, H, W, &route);
+    if (rc) return rc;
+    if (!buf || buflen < 1) return fail(AP_ERR_INVALID, "instnorm_bwd_route: bad buffer");
+    const char* g2 = has_g2 ? ",g2" : "";
+    switch (route) {
+    case INBWD_SMALL: snprintf(buf, buflen, "%s", has_g2 ? "small<g2>" : "small"); break;
+    case INBWD_VEC_256: snprintf(buf, buflen, "vec<256%s>", g2); break;
+    case INBWD_VEC_1024: snprintf(buf, buflen, "vec<1024%s>", g2); break;
+    case INBWD_FOLD1_256: snprintf(buf, buflen, "fold1<256%s>", g2); break;
+    case INBWD_FOLD1_1024: snprintf(buf, buflen, "fold1<1024%s>", g2); break;
+    case INBWD_GENERAL_256: snprintf(buf, buflen, "general<256>"); break;
+    case INBWD_GENERAL_1024: snprintf(buf, buflen, "general<1024>"); break;
+    case INBWD_BIG: snprintf(buf, buflen, "big"); break;
+    case INBWD_BIG_FOLD: snprintf(buf, buflen, "big<fold>"); break;
+    case INBWD_BIG_BF16: snprintf(buf, buflen, "big<bf16>"); break;
+    case INBWD_REDUCE_APPLY: snprintf(buf, buflen, "reduce_apply"); break;
+    }
+    return AP_OK;
 }
 
 int ap_instnorm_bwd_split_ok(int32_t C, int32_t H, int32_t W, int32_t g1_pad) {
@@ -1193,7 +1281,10 @@ int ap_act_bwd(const float* g1, int32_t g1_pad, const float* g2, const float* ou
     if (NC < 1 || NC > 65535) return fail(AP_ERR_UNSUPPORTED, "act_bwd: N*C=%d", NC);
     int bx = (H * W + 1023) / 1024;
     if (bx > 32) bx = 32;
-    if (g1_pad == 1 && (W & 3) == 0 && H >= 3 && W >= 4) {
+    ActBwdRoute route;
+    rc = act_bwd_route(g1_pad, H, W, &route);
+    if (rc) return rc;
+    if (route == ACTBWD_FOLD1) {
         hipLaunchKernelGGL(act_bwd_fold1_kernel, dim3((H * W / 4 + 511) / 512, NC), dim3(256), 0, (hipStream_t)stream, g1,
                            g2, out, act, H, W, dy);
         return check_launch("act_bwd_fold1_kernel");
@@ -1201,6 +1292,15 @@ int ap_act_bwd(const float* g1, int32_t g1_pad, const float* g2, const float* ou
     hipLaunchKernelGGL(act_bwd_kernel<false>, dim3(bx, NC), dim3(256), 0, (hipStream_t)stream, g1, g1_pad, g2, out, act, H, W,
                        dy, (float*)nullptr, 1);
     return check_launch("act_bwd_kernel");
+}
+
+int ap_act_bwd_route(int32_t g1_pad, int32_t H, int32_t W, char* buf, int32_t buflen) {
+    ActBwdRoute route;
+    int rc = act_bwd_route(g1_pad, H, W, &route);
+    if (rc) return rc;
+    if (!buf || buflen < 1) return fail(AP_ERR_INVALID, "act_bwd_route: bad buffer");
+    snprintf(buf, buflen, "%s", route == ACTBWD_FOLD1 ? "act_fold1" : "act_generic");
+    return AP_OK;
 }
 
 // act_bwd + the bias gradient db[c] = sum_{n, y, x} dy of the same layer in one pass (workspace: ap_act_bwd_bias_workspace_floats)

@@ -433,6 +433,11 @@ int ap_conv2d_wgrad(const ap_wgrad_desc* d, float* workspace, float* dw, ap_stre
 int ap_instnorm_bwd(const float* g1, int32_t g1_pad, const float* g2, const float* y, const float* mean,
                     const float* rstd, int32_t act, int32_t NC, int32_t H, int32_t W, float* sums_ws, float* dy,
                     ap_stream_t stream);
+/* Which kernel ap_instnorm_bwd launches for a plane geometry (no device is touched): the error the launcher returns for a refused
+ * g1_pad / act / geometry, else AP_OK and in buf one of  small, vec<256>, vec<1024>, fold1<256>, fold1<1024>  (each also with a
+ * second gradient: small<g2>, vec<256,g2>, ...),  general<256>, general<1024>, big, big<fold>, big<bf16>, reduce_apply.
+ * act_bits is the launcher's act argument (bit 8 included).  Tests use it to state which kernel a shape exercises. */
+int ap_instnorm_bwd_route(int32_t g1_pad, int32_t has_g2, int32_t act_bits, int32_t H, int32_t W, char* buf, int32_t buflen);
 /* The same backward for a layer whose gradient is only ever read by the bf16 matrix kernels (round 4): instead of the fp32 dy the
  * kernel writes the operands those kernels stage -- what ap_split_prepass and the weight gradient's own transposition would make
  * of dy in two more passes over it (autograd of networks.py:2329-2421 through nn.InstanceNorm2d / nn.ReLU):
@@ -465,6 +470,8 @@ int ap_conv2d_wgrad_xs(const ap_wgrad_desc* d, const void* g_xs, float* workspac
  * (out may then be NULL).  AP_ACT_TANH: 1 - out^2; RELU / LRELU: from the sign of the activated output. */
 int ap_act_bwd(const float* g1, int32_t g1_pad, const float* g2, const float* out, int32_t act, int32_t NC,
                int32_t H, int32_t W, float* dy, ap_stream_t stream);
+/* Which kernel ap_act_bwd launches: act_fold1 (pad-1 fold with W % 4 == 0, H >= 3) or act_generic; errors as the launcher's. */
+int ap_act_bwd_route(int32_t g1_pad, int32_t H, int32_t W, char* buf, int32_t buflen);
 /* ap_act_bwd of a layer WITHOUT InstanceNorm together with its bias gradient db[c] = sum_{n,y,x} dy[n][c][y][x] (fixed summation order):
  * the block sums of dy are formed while it is written, no second pass over it.  workspace: ap_act_bwd_bias_workspace_floats() floats. */
 int64_t ap_act_bwd_bias_workspace_floats(int32_t N, int32_t C, int32_t H, int32_t W);
