@@ -57,6 +57,13 @@ SIGNATURES.update({
 })
 MAX_JPEG_SIDE = 2048
 
+# the coloured landmark rasteriser (csrc/data/landmark_vis.hip), added the same way
+_u32 = ctypes.c_uint32
+SIGNATURES.update({
+    'apd_landmark_vis_ok': (ctypes.c_int32, [_ptr] * 5 + [_i32] * 8 + [_u32, _u32, _ptr]),
+    'apd_landmark_vis': (ctypes.c_int, [_ptr] * 5 + [_i32] * 8 + [_u32, _u32, _ptr, _ptr]),
+})
+
 _lib = None
 _lock = threading.Lock()
 

@@ -8,7 +8,10 @@
   * ``encode_png_batch`` complete PNG files made on the device (apd_png_encode); ``save_png_batch(encoder='device')`` writes
     them, and the pool is left with the write() calls,
   * ``encode_jpeg_batch`` complete baseline JPEG files made on the device (apd_jpeg_encode): the frames of the MJPEG clip
-    ``end2end.py --video avi`` writes through util/avi.py.
+    ``end2end.py --video avi`` writes through util/avi.py,
+  * ``landmark_vis``   landmark sets drawn as coloured contours in painter's order (apd_landmark_vis): vis_landmark of
+    main_end2end_module2.py:47-68 with ``FACE_CONTOURS``, the frames of ``end2end.py --landmark_video avi`` and the marked photo
+    of ``--side_outputs``.
 
 A missing library or a refused call raises; nothing here falls back to the host."""
 import concurrent.futures
@@ -85,6 +88,69 @@ def landmark_marks(frames, lm, win, hradius=3):
     with torch.cuda.device(frames.device):
         D.check(D.lib().apd_landmark_marks(_p(frames), _p(lm), _p(win), n, c, lm.shape[1], h, w, int(hradius), _p(out),
                                            _stream(frames.device)), 'landmark_marks')
+    return out
+
+
+def _face_contours():
+    """The drawing vis_landmark (main_end2end_module2.py:47-68) makes of a 68-point face, as a table: every curve joins the
+    landmarks first .. last + 1 in turn, a closed one then joins first to last + 1; colours are the reference's BGR tuples read
+    as RGB, because it writes the picture with cv2.imwrite."""
+    curves = (('jaw', 0, 15, False, 0x1990FF), ('brow', 17, 20, False, 0x32CD32), ('brow', 22, 25, False, 0x32CD32),
+              ('nose', 27, 34, False, 0x3FE0D0), ('eye', 36, 40, True, 0xFF6347), ('eye', 42, 46, True, 0xFF6347),
+              ('mouth', 48, 58, True, 0xEE82EE), ('mouth', 60, 66, True, 0xEE82EE))
+    seg, rgb = [], []
+    for _, first, last, closed, colour in curves:
+        pairs = [(i, i + 1) for i in range(first, last + 1)] + ([(first, last + 1)] if closed else [])
+        seg += pairs
+        rgb += [colour] * len(pairs)
+    return {'segments': np.array(seg, np.int32), 'colours': np.array(rgb, np.uint32), 'disc_rgb': 0xFF0000, 'points': 68}
+
+
+FACE_CONTOURS = _face_contours()      # 64 segments in draw order, their five colours, the red of the landmark discs
+
+
+def face_contour_style(height):
+    """(thickness, radius) vis_landmark draws with at this frame height: 2 (height // 256) and height // 256"""
+    return 2 * (height // 256), height // 256
+
+
+def landmark_vis(pts, seg, seg_rgb, height, width, radius, thickness, disc_rgb, bg_rgb=0xFFFFFF, bg=None):
+    """pts (N, P, 2) integer (x, y), a device tensor or a host array; seg (S, 2) host integer table or None; seg_rgb (S,)
+    0xRRGGBB per segment; bg None (the constant bg_rgb) or a device (1 | N, 3, height, width) float tensor -> (N, 3, height,
+    width) float32 on the device: the segments drawn in order as cv2.line, then every point as a filled disc of disc_rgb
+    (radius -1: none), later marks on top (apd_landmark_vis).  The caller makes the coordinates integers by the rule of the
+    call site it mirrors; a floating-point `pts` is refused."""
+    if not torch.is_tensor(pts):
+        a = np.asarray(pts)
+        if a.dtype.kind not in 'iu':
+            raise ValueError('landmark_vis: pts must be integers (found %s): truncate or round them as the mirrored call site does' % a.dtype)
+        pts = torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).cuda()
+    if pts.is_floating_point() or pts.dtype == torch.bool or not pts.is_cuda or pts.dim() != 3 or pts.shape[2] != 2:
+        raise ValueError('landmark_vis: pts must be an (N, P, 2) integer tensor on the device')
+    pts = pts.to(torch.int32).contiguous()
+    n, p, _ = pts.shape
+    host = np.zeros((0, 2), np.int32) if seg is None else np.ascontiguousarray(np.asarray(seg, dtype=np.int32)).reshape(-1, 2)
+    s = int(host.shape[0])
+    dev = rgb = None
+    if s:
+        colours = np.ascontiguousarray(np.asarray(seg_rgb, dtype=np.uint32)).reshape(-1)
+        if colours.shape[0] != s:
+            raise ValueError('landmark_vis: %d segments, %d colours' % (s, colours.shape[0]))
+        key = (str(pts.device), host.tobytes(), colours.tobytes())
+        if key not in _SEG:
+            _SEG[key] = (torch.from_numpy(host).to(pts.device), torch.from_numpy(colours.view(np.int32)).to(pts.device))
+        dev, rgb = _SEG[key]
+    bg_frames = 1
+    if bg is not None:
+        bg = _device_f32(bg, 'landmark_vis', 4)
+        bg_frames = bg.shape[0]
+        if tuple(bg.shape[1:]) != (3, height, width) or bg.device != pts.device:
+            raise ValueError('landmark_vis: bg %s, expected (1 | N, 3, %d, %d) on %s' % (tuple(bg.shape), height, width, pts.device))
+    out = torch.empty((n, 3, height, width), dtype=torch.float32, device=pts.device)
+    with torch.cuda.device(pts.device):
+        D.check(D.lib().apd_landmark_vis(_p(pts), _p(dev), host.ctypes.data_as(ctypes.c_void_p) if s else None, _p(rgb), _p(bg), bg_frames,
+                                         n, p, s, height, width, int(radius), int(thickness), int(disc_rgb) & 0xFFFFFF,
+                                         int(bg_rgb) & 0xFFFFFF, _p(out), _stream(pts.device)), 'landmark_vis')
     return out
 
 

@@ -6,6 +6,8 @@ geomcgt_ifw_test`` (which re-reads them, builds the motion grids with scipy on t
 copies the PNGs it wrote and calls ffmpeg at 62.5 fps.  Here: photo + a landmark clip in, frames (and the video, when
 ffmpeg exists) out, through ``stream.ClipStreamer`` in batches.  ``--video avi`` needs no ffmpeg: the frames are encoded as
 JPEG on the GPU and muxed with the sound into ``<out>/output.avi`` here (util/avi.py); ``--frames none`` then skips the PNGs.
+``--landmark_video avi`` adds ``<out>/landmark_seq2.avi``, the driving landmarks as coloured face contours (:47-68, 303), and
+``--side_outputs`` adds ``photo.png`` and ``ori_view.png`` (:286, 328-331): what the generator was given, drawn on the GPU.
 
     python -m animateportrait_amd.end2end --photo face.png --landmarks Data/Alm_txt/MTCNN/<db>_MTCNN \\
         --landmark_scale 0.5 --name formal/drawing --epoch 70 --out output/<db> [--audio a.wav]
@@ -131,27 +133,40 @@ def make_parser():
                          'frames, otherwise 3')
     ap.add_argument('--frames', choices=('png', 'none'), default='png',
                     help='none: write no per-frame PNG (only with --video avi)')
+    ap.add_argument('--landmark_video', choices=('none', 'avi'), default='none',
+                    help='avi: also write <out>/landmark_seq2.avi, the landmark sequence that drives the clip drawn as coloured face '
+                         'contours on white (apd_landmark_vis on the GPU), at --fps with the sound of --audio / --wav')
+    ap.add_argument('--landmark_video_size', type=_landmark_video_size, default=512,
+                    help='with --landmark_video avi: side of its square frames, 256 .. 1024 (lines are 2 (size // 256) px thick)')
+    ap.add_argument('--landmark_video_quality', type=int, default=90, help='with --landmark_video avi: JPEG quality 1..100')
+    ap.add_argument('--side_outputs', action='store_true',
+                    help='also write <out>/photo.png (the photo at --size) and <out>/ori_view.png (the photo with a red disc on each '
+                         'of its landmarks), through --png_encoder')
     return ap
 
 
-def write_avi(frames, path, fps, audio=None, batch=16, channels=None, quality=90):
-    """frames (T, C, H, W) -> an AVI file of MJPG frames (util/avi.py) with the PCM sound of the wav `audio`.  The frames are
-    encoded where they are, --batch at a time (data/visuals.encode_jpeg_batch), into two pinned buffers in turn, and a writer
-    thread appends a batch to the file while the next is encoded: the pattern of write_frames."""
+def _landmark_video_size(text):
+    size = int(text)
+    if not 256 <= size <= 1024:
+        raise argparse.ArgumentTypeError('%d, served: 256 .. 1024 (below 256 the line thickness 2 (size // 256) is 0)' % size)
+    return size
+
+
+def write_avi_batches(batches, path, width, height, fps, audio=None, channels=3, quality=90, slot='clip'):
+    """batches: an iterable of (n, C, height, width) device tensors, made one at a time -> an AVI file of MJPG frames
+    (util/avi.py) with the PCM sound of the wav `audio`.  A batch is encoded where it is (data/visuals.encode_jpeg_batch) into
+    two pinned buffers in turn, and a writer thread appends it to the file while the next is made and encoded: the pattern of
+    write_frames.  Only the batch in hand is alive, so a clip never has to exist as a whole."""
     import concurrent.futures
     from .data import visuals
     from .util import avi
-    if not frames.is_cuda:
-        frames = frames.cuda()
-    if channels is None:
-        channels = 1 if frames.shape[1] == 1 else 3
     num, den = avi.fps_fraction(fps)
-    writer = avi.AviWriter(path, frames.shape[3], frames.shape[2], num, den, audio=audio)
+    writer = avi.AviWriter(path, width, height, num, den, audio=audio)
     pending = None
     with concurrent.futures.ThreadPoolExecutor(max_workers=1) as pool:
         try:
-            for turn, k0 in enumerate(range(0, frames.shape[0], batch)):
-                buf, sizes = visuals.encode_jpeg_batch(frames[k0:k0 + batch], channels=channels, quality=quality, slot='clip%d' % (turn & 1))
+            for turn, frames in enumerate(batches):
+                buf, sizes = visuals.encode_jpeg_batch(frames, channels=channels, quality=quality, slot='%s%d' % (slot, turn & 1))
                 done = torch.cuda.Event()
                 done.record()
                 if pending is not None:
@@ -163,6 +178,53 @@ def write_avi(frames, path, fps, audio=None, batch=16, channels=None, quality=90
         finally:
             writer.close()
     return writer.frames
+
+
+def write_avi(frames, path, fps, audio=None, batch=16, channels=None, quality=90):
+    """frames (T, C, H, W) -> an AVI file, --batch frames at a time through write_avi_batches."""
+    if not frames.is_cuda:
+        frames = frames.cuda()
+    if channels is None:
+        channels = 1 if frames.shape[1] == 1 else 3
+    return write_avi_batches((frames[k0:k0 + batch] for k0 in range(0, frames.shape[0], batch)), path, frames.shape[3],
+                             frames.shape[2], fps, audio, channels, quality)
+
+
+def truncated_landmarks(seq, scale):
+    """(T, P, 2) float landmarks scaled and made int32 as vis_landmark makes them (main_end2end_module2.py:49: astype('int32'),
+    truncation toward zero); NaN goes to 0 and anything beyond +-2^20 to that bound, where the cast is still defined."""
+    a = np.nan_to_num(np.asarray(seq, dtype=np.float64) * scale, nan=0.0)
+    return np.clip(a, -2.0 ** 20, 2.0 ** 20).astype(np.int32)
+
+
+def write_landmark_avi(seq, path, fps, device, audio=None, batch=16, size_in=256, size_out=512, quality=90):
+    """The predicted landmark sequence as coloured face contours on white, the counterpart of landmark_seq2.mov
+    (main_end2end_module2.py:281, 303): seq (T, 68, 2) in pixels of a size_in frame -> MJPG frames of size_out x size_out.  The
+    integer landmarks are uploaded once; a batch of frames is drawn by one apd_landmark_vis launch when the encoder asks for it."""
+    from .data import visuals
+    table = visuals.FACE_CONTOURS
+    thickness, radius = visuals.face_contour_style(size_out)
+    pts = torch.from_numpy(truncated_landmarks(seq, size_out / float(size_in))).to(device)
+
+    def batches():
+        for k0 in range(0, pts.shape[0], batch):
+            yield visuals.landmark_vis(pts[k0:k0 + batch], table['segments'], table['colours'], size_out, size_out, radius, thickness,
+                                       table['disc_rgb'])
+    with torch.cuda.device(device):
+        return write_avi_batches(batches(), path, size_out, size_out, fps, audio, 3, quality, slot='landmarks')
+
+
+def write_side_outputs(photo, lm0, out_dir, device, encoder='host'):
+    """<out_dir>/photo.png: the photo as the generator sees it; <out_dir>/ori_view.png: the same with a red disc on every photo
+    landmark (main_end2end_module2.py:286, 328-331 draws radius 5 at 512 px: round(5 size / 512) here), coordinates by Python's round."""
+    from .data import visuals
+    size = photo.shape[-1]
+    photo = photo.to(device).float().contiguous()
+    pts = np.clip(np.rint(np.nan_to_num(np.asarray(lm0, dtype=np.float64)[:, :2])), -2.0 ** 20, 2.0 ** 20).astype(np.int32)[None]
+    marked = visuals.landmark_vis(pts, None, None, size, size, round(5 * size / 512), 1, visuals.FACE_CONTOURS['disc_rgb'], bg=photo)
+    names = {'photo': [os.path.join(out_dir, 'photo.png')], 'ori_view': [os.path.join(out_dir, 'ori_view.png')]}
+    with torch.cuda.device(device):
+        return visuals.save_png_batch({'photo': photo, 'ori_view': marked}, names, encoder=encoder)
 
 
 def write_frames(frames, fdir, encoder='host', batch=16, channels=3):
@@ -211,6 +273,8 @@ def main(argv=None, prepare_model=None):
         ap.error('--frames none leaves nothing to assemble: it needs --video avi')
     if not 1 <= a.video_quality <= 100:
         ap.error('--video_quality %d, served: 1 .. 100' % a.video_quality)
+    if not 1 <= a.landmark_video_quality <= 100:
+        ap.error('--landmark_video_quality %d, served: 1 .. 100' % a.landmark_video_quality)
     if a.wav is not None and not a.no_autovc and not os.path.exists(a.load_AUTOVC_name):
         ap.error('--wav: AutoVC checkpoint %s not found; the reference converts the spectrogram before Module1 '
                  '(pass --load_AUTOVC_name, or --no_autovc to feed the raw mel on purpose)' % a.load_AUTOVC_name)
@@ -237,6 +301,17 @@ def main(argv=None, prepare_model=None):
     matte = load_matte(a.matte, a.size) if a.matte else None
     if matte is None and model.aux.get('modnet') is None:
         raise SystemExit('no matting network is attached (aux["modnet"]): pass --matte PNG')
+    # the previews come first: they show what the generator is about to be given, whatever becomes of the clip
+    device = torch.device('cuda', opt.gpu_ids[0])
+    if a.side_outputs:
+        os.makedirs(a.out, exist_ok=True)
+        write_side_outputs(photo, lm0, a.out, device, a.png_encoder)
+        print('wrote photo.png and ori_view.png to', a.out)
+    if a.landmark_video == 'avi':
+        os.makedirs(a.out, exist_ok=True)
+        preview = os.path.join(a.out, 'landmark_seq2.avi')
+        write_landmark_avi(seq, preview, a.fps, device, a.audio, a.batch, a.size, a.landmark_video_size, a.landmark_video_quality)
+        print('landmark preview is', preview)
     frames = stream.ClipStreamer(model, batch=a.batch, triangulate=a.triangulate).run(photo, lm0, seq, matte=matte)
     fdir = os.path.join(a.out, 'frames')
     if a.frames == 'png':

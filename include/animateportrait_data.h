@@ -193,6 +193,37 @@ int32_t apd_jpeg_encode_ok(const float* src, const uint8_t* dst, const int32_t* 
 int apd_jpeg_encode(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, int32_t channels, int32_t quality,
                     uint8_t* dst, int64_t slot_bytes, int32_t* sizes, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- the landmark preview: landmark sets drawn as coloured contours (end2end.py --landmark_video avi, --side_outputs).
+ * Added as above: APD_ABI_VERSION stays 1. */
+
+/* vis_landmark (main_end2end_module2.py:47-68) for a batch, and with S == 0 and `bg` the photo marked with its landmarks.
+ *   pts       device (N, P, 2) int32 (x, y): the caller has made them integers by the rule of the call site it mirrors
+ *             (astype(int32) truncation in vis_landmark, Python round for the marked photo); clamped to +-2^20 here
+ *   seg       device (S, 2) int32 landmark indices in draw order; seg_host the same table on the host: every index is checked
+ *             against P here, before the launch, and the kernel clamps what it reads from `seg` into [0, P) -- the contract of
+ *             apd_landmark_map.  Both, and seg_rgb, may be null when S == 0
+ *   seg_rgb   device (S,) uint32, 0x00RRGGBB: one colour per segment
+ *   bg        null: the background is the constant bg_rgb.  Else device (bg_frames, 3, H, W) float32 with bg_frames == 1 (one
+ *             picture shared by every frame) or N; where nothing is drawn its values pass through bit for bit.  It must not
+ *             overlap out (refused)
+ *   out       device (N, 3, H, W) float32, planes R, G, B; every element is written exactly once: no memset is needed, no
+ *             atomic is used, and the same input gives the same bits
+ * Draw order, a later primitive overwriting an earlier one: the background; segments 0 .. S-1, each as
+ * cv2.line(p0, p1, colour, thickness) by the rule apd_landmark_map states for op 1 (thickness 1 included); then all P discs
+ * cv2.circle(p, radius, disc_rgb, -1).  radius -1 draws no disc.  Primitives are clipped to the frame.
+ * A drawn byte v is stored as (2 v + 1) / 255 - 1 (evaluated in double, rounded to float32 once): the middle of v's bucket under
+ * apd_frames_to_u8's (uint8)((x + 1) / 2 * 255), which therefore returns v for every v in 0..255 -- the PNG and JPEG encoders and
+ * tensor2im all see exactly the colour bytes.
+ * One launch on `stream`.  Served: N 1..65535, P 1..APD_MAX_POINTS, S 0..APD_MAX_SEGMENTS, H, W 1..APD_MAX_MAP, radius
+ * -1..APD_MAX_RADIUS, thickness 1..APD_MAX_THICKNESS.  apd_landmark_vis_ok needs no device and checks everything but the device
+ * pointers' contents. */
+int32_t apd_landmark_vis_ok(const int32_t* pts, const int32_t* seg, const int32_t* seg_host, const uint32_t* seg_rgb,
+                            const float* bg, int32_t bg_frames, int32_t N, int32_t P, int32_t S, int32_t H, int32_t W,
+                            int32_t radius, int32_t thickness, uint32_t disc_rgb, uint32_t bg_rgb, const float* out);
+int apd_landmark_vis(const int32_t* pts, const int32_t* seg, const int32_t* seg_host, const uint32_t* seg_rgb,
+                     const float* bg, int32_t bg_frames, int32_t N, int32_t P, int32_t S, int32_t H, int32_t W,
+                     int32_t radius, int32_t thickness, uint32_t disc_rgb, uint32_t bg_rgb, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
