@@ -161,6 +161,8 @@ SIGNATURES = {
                                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), c_f32p, c_f32p, ctypes.c_int32,
                                              ctypes.c_void_p]),
     'ap_conv2d_wgrad_gt_dims': (ctypes.c_int, [ctypes.POINTER(ApWgradDesc), ctypes.POINTER(ctypes.c_int32)]),
+    'ap_conv2d_wgrad_route': (ctypes.c_int, [ctypes.POINTER(ApWgradDesc), ctypes.c_char_p, ctypes.c_int32]),
+    'ap_conv2d_wgrad_route_names': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32]),
     'ap_conv2d_wgrad_pre': (ctypes.c_int, [ctypes.POINTER(ApWgradDesc), ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p]),
     'ap_conv2d_wgrad_xs_ok': (ctypes.c_int32, [ctypes.POINTER(ApWgradDesc)]),
     'ap_conv2d_wgrad_xs': (ctypes.c_int, [ctypes.POINTER(ApWgradDesc), ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p]),

@@ -23,6 +23,7 @@
 #include <atomic>
 #include <climits>
 #include <cstring>
+#include <string>
 
 namespace apamd {
 
@@ -352,55 +353,66 @@ static int launch_pad(const ap_src* segs, int nseg, int N, int C, int H, int W, 
     return check_launch("pad_materialize_kernel");
 }
 
+// which of the four operand-preparation kernels re-tiles an operand (launch_split_transpose launches it, ap_conv2d_wgrad_route names
+// it), or one of the two refusals.  any_b16: a segment holds bf16 values (ap_src.act bit 8); W: the source's width
+enum SplitTForm { ST_GENERAL, ST_VEC, ST_PAD_ROWS, ST_S2D_ROWS, ST_NO_ROW_VIEW = -1, ST_B16_NEEDS_PAD_ROWS = -2 };
+static bool split_transpose_whole_rows(int W, int s2d_c) { return W == 64 || W == 128 || W == 256 || (W == 32 && s2d_c == 0); }
+static int split_transpose_form(int nseg, bool any_b16, int C, int W, int pad, int X8, int Cp, int s2d_c, int rows_k) {
+    const bool whole_rows = split_transpose_whole_rows(W, s2d_c);
+    const bool pad_rows = whole_rows && s2d_c == 0 && pad == 1;
+    if (rows_k > 0) return (any_b16 || s2d_c) ? ST_NO_ROW_VIEW : ST_GENERAL;      // the row view exists in the general kernel only
+    if (any_b16 && !pad_rows) return ST_B16_NEEDS_PAD_ROWS;
+    if (nseg == 1 && pad == 0 && s2d_c == 0 && X8 * 8 == W) return ST_VEC;
+    if (pad_rows) return ST_PAD_ROWS;
+    if (whole_rows && s2d_c > 0 && s2d_c % 32 == 0 && nseg == 1 && C == 4 * s2d_c && Cp == C) return ST_S2D_ROWS;
+    return ST_GENERAL;
+}
+static int split_transpose_refusal(int form) {
+    if (form == ST_NO_ROW_VIEW) return fail(AP_ERR_UNSUPPORTED, "split_transpose: row view of a bf16 / space-to-depth source");
+    return fail(AP_ERR_UNSUPPORTED, "split_transpose: a bf16 source needs the padded-row form (pad 1, W in {32, 64, 128, 256})");
+}
+static bool any_bf16_segment(const ap_src* segs, int nseg) {
+    for (int s = 0; s < nseg; ++s)
+        if ((segs[s].act >> 8) & 1) return true;
+    return false;
+}
+
 static int launch_split_transpose(const ap_src* segs, int nseg, int N, int C, int H, int W, int pad, int pad_mode,
                                   int Hp, int X8, int Cp, uint4* out, hipStream_t stream, int s2d_c, int heads_only, int rows_k = 0) {
     SplitTParams p;
     memset(&p, 0, sizeof(p));
     p.nseg = nseg;
     int cbeg = 0;
-    bool any_b16 = false;
     for (int s = 0; s < nseg; ++s) {
         fill_seg(p.seg[s], segs[s], cbeg);
         // ap_src.act bit 8: the segment's data are bf16 values (a raw output of ap_conv2d_fwd_bf16out); only the padded-row kernel reads those
         p.seg[s].act = segs[s].act & 0xff;
         p.seg[s].pad_ = (segs[s].act >> 8) & 1;
-        any_b16 = any_b16 || p.seg[s].pad_;
         cbeg += segs[s].C;
     }
     p.N = N; p.C = C; p.H = H; p.W = W; p.pad = pad; p.pad_mode = pad_mode; p.Hp = Hp; p.X8 = X8; p.Cp = Cp; p.out = out;
     p.s2d_c = s2d_c;
     p.heads_only = heads_only;
     p.rows_k = rows_k;
-    const bool whole_rows = W == 64 || W == 128 || W == 256 || (W == 32 && s2d_c == 0);
-    const bool pad_rows = whole_rows && s2d_c == 0 && pad == 1;
-    enum { GENERAL, VEC, PAD_ROWS, S2D_ROWS } form = GENERAL;
-    if (rows_k > 0) {                                 // the row view exists in the general kernel only
-        if (any_b16 || s2d_c) return fail(AP_ERR_UNSUPPORTED, "split_transpose: row view of a bf16 / space-to-depth source");
-    } else if (any_b16 && !pad_rows) {
-        return fail(AP_ERR_UNSUPPORTED, "split_transpose: a bf16 source needs the padded-row form (pad 1, W in {32, 64, 128, 256})");
-    } else if (nseg == 1 && pad == 0 && s2d_c == 0 && X8 * 8 == W) {
-        form = VEC;
-    } else if (pad_rows) {
-        form = PAD_ROWS;
-    } else if (whole_rows && s2d_c > 0 && s2d_c % 32 == 0 && nseg == 1 && C == 4 * s2d_c && Cp == C) {
-        form = S2D_ROWS;
-    }
+    const bool whole_rows = split_transpose_whole_rows(W, s2d_c);
+    const int form = split_transpose_form(nseg, any_bf16_segment(segs, nseg), C, W, pad, X8, Cp, s2d_c, rows_k);
+    if (form < 0) return split_transpose_refusal(form);
     if (N > 65535 || Cp / 64 > 65535) return fail(AP_ERR_UNSUPPORTED, "split_transpose: N=%d C=%d", N, C);
     const int R = whole_rows ? 256 / W : 1;                                       // source rows per workgroup of the row forms
     const size_t row_lds = (size_t)64 * (R * X8 * 8 + 1) * sizeof(float);
     int rc = AP_OK;
     switch (form) {
-    case VEC: {         // unpadded operand with whole octet rows: 16-byte loads, 1 KiB per wave
+    case ST_VEC: {      // unpadded operand with whole octet rows: 16-byte loads, 1 KiB per wave
         const size_t lds = 64 * 257 * sizeof(float);
         if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&split_transpose_vec_kernel), (int)lds))) return rc;
         hipLaunchKernelGGL(split_transpose_vec_kernel, dim3((Hp * X8 + 31) / 32, Cp / 64, N), dim3(256), lds, stream, p);
         return check_launch("split_transpose_vec_kernel");
     }
-    case PAD_ROWS:      // padded rows, 16-byte loads
+    case ST_PAD_ROWS:   // padded rows, 16-byte loads
         if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&split_transpose_pad_kernel), 96 * 1024))) return rc;
         hipLaunchKernelGGL(split_transpose_pad_kernel, dim3((Hp + R - 1) / R, Cp / 64, N), dim3(256), row_lds, stream, p);
         return check_launch("split_transpose_pad_kernel");
-    case S2D_ROWS:      // space-to-depth view, whole source rows
+    case ST_S2D_ROWS:   // space-to-depth view, whole source rows
         if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&split_transpose_s2d_kernel), 96 * 1024))) return rc;
         hipLaunchKernelGGL(split_transpose_s2d_kernel, dim3(((Hp + R - 1) / R) * 2, s2d_c / 32, N), dim3(256), row_lds, stream, p);
         return check_launch("split_transpose_s2d_kernel");
@@ -480,13 +492,19 @@ static int launch_bf16_gemm_operand(const ap_wgrad_desc* d, const WgradPlan& pl,
     return launch_xs_transpose(d->src_xs, cs, d->nsrc, d->N, d->H, d->W, d->pad, d->pad_mode, b.Hp, b.AX8, b.Cp, parts, at, stream);
 }
 
+// the kernel table entry of a bf16 GEMM plan (b16: plain-bf16 arithmetic)
+static const WgradBf3Kernel* bf3_kernel(const Bf16GemmPlan& b, bool b16) {
+    const WgradBf3Kernel* k = nullptr;
+    for (const auto& c : kWgradBf3Kernels)
+        if (c.K == b.Kb && c.form == (b.wide ? BF3_WIDE : (b16 ? BF3_HEADS : BF3_SPLIT))) k = &c;
+    return k;
+}
+
 static int launch_bf16_gemm(const ap_wgrad_desc* d, const WgradPlan& pl, const void* g_t, bool from_xs, float* workspace, float* dw,
                             hipStream_t stream) {
     const Bf16GemmPlan& b = pl.bf;
     const bool b16 = d->precision == AP_PRECISION_BF16;
-    const WgradBf3Kernel* k = nullptr;
-    for (const auto& c : kWgradBf3Kernels)
-        if (c.K == b.Kb && c.form == (b.wide ? BF3_WIDE : (b16 ? BF3_HEADS : BF3_SPLIT))) k = &c;
+    const WgradBf3Kernel* k = bf3_kernel(b, b16);
     if (!k) return fail(AP_ERR_UNSUPPORTED, b.wide ? "wgrad: no 8-wave kernel for k=%d" : "wgrad: no split-bf16 kernel for k=%d", b.Kb);
     int rc = ensure_dyn_lds(k->fn, 160 * 1024);
     if (rc) return rc;
@@ -604,6 +622,94 @@ static const WgradXsKernel kWgradXsKernels[] = {
     {3, 1, 2, &launch_wgrad_xs<WgradXsCfg<3, 1, 2>>}, {3, 2, 2, &launch_wgrad_xs<WgradXsCfg<3, 2, 2>>},
     {3, 2, 4, &launch_wgrad_xs<WgradXsCfg<3, 2, 4>>}, {4, 2, 2, &launch_wgrad_xs<WgradXsCfg<4, 2, 2>>},
 };
+static const WgradXsKernel* xs_kernel(const ap_wgrad_desc* d, const Bf16GemmPlan& b) {
+    const int parts = d->precision == AP_PRECISION_BF16 ? 1 : 2, wm = b.wide ? 4 : 2;
+    const WgradXsKernel* k = nullptr;
+    for (const auto& c : kWgradXsKernels)
+        if (c.Kb == b.Kb && c.parts == parts && c.wm == wm) k = &c;
+    return k;
+}
+
+// ------------------------------------------------------------------ the plan as text (ap_conv2d_wgrad_route)
+// how an operand reaches its kernel: through one of the four split_transpose kernels (by SplitTForm), re-tiled from the forward pass's
+// split copies, padded in fp32 for the igemm kernel, read where it lies, or not at all (the caller brings it)
+static const char* const kSplitTForms[] = {"general", "vec", "pad_rows", "s2d_rows"};
+static const char* const kOtherForms[] = {"xs_transpose", "pad", "direct", "none"};
+static const char* const kBf3Forms[] = {"split", "heads", "wide"};
+
+static void bf3_name(const WgradBf3Kernel& k, char* out, int n) {
+    // K = 2 is only ever the space-to-depth view, K = 7 the row view (kWgradBf3Kernels)
+    snprintf(out, n, "bf16gemm<%d,%s>%s", k.K, kBf3Forms[k.form], k.K == 2 ? "+s2d" : (k.K == 7 ? "+rows" : ""));
+}
+
+// what wgrad_impl would launch for this descriptor, from the same plan: nothing is launched, no pointer is followed
+static int wgrad_route_text(const ap_wgrad_desc* d, char* buf, int n) {
+    WgradPlan pl;
+    int rc = make_wgrad_plan(d, pl);
+    if (rc) return rc;
+    if (!buf || n < 1) return fail(AP_ERR_INVALID, "wgrad_route: bad buffer");
+    char kernel[64], xs[32] = "";
+    const char *g = "direct", *a = "direct";
+    switch (pl.family) {
+    case WgradFamily::Narrow:
+        snprintf(kernel, sizeof(kernel), "narrow<%d,%d,%d,%d>", pl.narrow.k->K, pl.narrow.k->S, pl.narrow.k->Cin, pl.narrow.k->ppt);
+        break;
+    case WgradFamily::Bf16Gemm: {
+        const Bf16GemmPlan& b = pl.bf;
+        const WgradBf3Kernel* k = bf3_kernel(b, d->precision == AP_PRECISION_BF16);
+        if (!k) return fail(AP_ERR_UNSUPPORTED, b.wide ? "wgrad: no 8-wave kernel for k=%d" : "wgrad: no split-bf16 kernel for k=%d", b.Kb);
+        bf3_name(*k, kernel, sizeof(kernel));
+        // (the arguments of launch_bf16_gemm's two launch_split_transpose calls)
+        // no gradient tensor: the caller brings that operand prepared (ap_conv2d_wgrad_pre) or as a split copy (ap_conv2d_wgrad_xs)
+        const bool a_xs = wgrad_xs_route(d, pl), g_own = d->g.data != nullptr;
+        int fa = ST_GENERAL, fg = ST_GENERAL;
+        if (!a_xs)
+            fa = split_transpose_form(d->nsrc, any_bf16_segment(d->src, d->nsrc), b.Cb, d->W, b.s2d ? 0 : d->pad, b.AX8, b.Cp,
+                                      b.s2d ? pl.Cin : 0, b.rows ? b.Kb : 0);
+        if (g_own) fg = split_transpose_form(1, any_bf16_segment(&d->g, 1), d->M, d->GW, 0, b.GX8, b.Mp, 0, 0);
+        if (fa < 0 || fg < 0) return split_transpose_refusal(fa < 0 ? fa : fg);
+        a = a_xs ? "xs_transpose" : kSplitTForms[fa];
+        g = g_own ? kSplitTForms[fg] : "none";
+        if (wgrad_xs_direct_ok(d, pl))
+            if (const WgradXsKernel* x = xs_kernel(d, b)) snprintf(xs, sizeof(xs), " xs<%d,%d,%d>", x->Kb, x->parts, x->wm);
+        break;
+    }
+    default:
+        snprintf(kernel, sizeof(kernel), "igemm<%d,%d,%d,%d,%d>", pl.k->S, pl.k->K, pl.k->M_TILE, pl.k->Q_TILE, pl.k->PR);
+        a = "pad";
+        g = pl.ig.g_direct ? "direct" : "pad";
+    }
+    snprintf(buf, n, "%s g=%s a=%s P=%d nstages=%d%s", kernel, g, a, pl.P, pl.nstages, xs);
+    return AP_OK;
+}
+
+// every kernel table entry and operand form ap_conv2d_wgrad_route can name, one per line
+static int wgrad_route_names(char* buf, int n) {
+    if (!buf || n < 1) return fail(AP_ERR_INVALID, "wgrad_route_names: bad buffer");
+    std::string all;
+    char name[64];
+    for (const auto& k : kWgradNarrowKernels) {
+        snprintf(name, sizeof(name), "narrow<%d,%d,%d,%d>\n", k.K, k.S, k.Cin, k.ppt);
+        all += name;
+    }
+    for (const auto& k : kWgradBf3Kernels) {
+        bf3_name(k, name, sizeof(name));
+        all += name;
+        all += "\n";
+    }
+    for (const auto& k : kWgradKernels) {
+        snprintf(name, sizeof(name), "igemm<%d,%d,%d,%d,%d>\n", k.S, k.K, k.M_TILE, k.Q_TILE, k.PR);
+        all += name;
+    }
+    for (const auto& k : kWgradXsKernels) {
+        snprintf(name, sizeof(name), "xs<%d,%d,%d>\n", k.Kb, k.parts, k.wm);
+        all += name;
+    }
+    for (const char* f : kSplitTForms) all += std::string(f) + "\n";
+    for (const char* f : kOtherForms) all += std::string(f) + "\n";
+    snprintf(buf, n, "%s", all.c_str());
+    return (int)all.size() < n ? AP_OK : fail(AP_ERR_INVALID, "wgrad_route_names: %d bytes needed", (int)all.size() + 1);
+}
 
 // ------------------------------------------------------------------ the 7x7 edge layers and the PatchGAN's first layer (wgrad_k7.h)
 struct K7Plan {
@@ -719,6 +825,10 @@ int ap_conv2d_wgrad_gt_dims(const ap_wgrad_desc* d, int32_t* dims) {
     return 1;
 }
 
+int ap_conv2d_wgrad_route(const ap_wgrad_desc* d, char* buf, int32_t buflen) { return wgrad_route_text(d, buf, buflen); }
+
+int ap_conv2d_wgrad_route_names(char* buf, int32_t buflen) { return wgrad_route_names(buf, buflen); }
+
 int ap_conv2d_wgrad(const ap_wgrad_desc* d, float* workspace, float* dw, ap_stream_t stream) {
     return wgrad_impl(d, nullptr, workspace, dw, stream);
 }
@@ -765,11 +875,10 @@ int ap_conv2d_wgrad_xs(const ap_wgrad_desc* d, const void* g_xs, float* workspac
     }
     p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.nstages = pl.nstages; p.P = pl.P; p.m_tiles = pl.m_tiles; p.c_tiles = b.c_tiles;
     p.partial = workspace;
-    const int parts = d->precision == AP_PRECISION_BF16 ? 1 : 2, wm = b.wide ? 4 : 2;
-    const WgradXsKernel* k = nullptr;
-    for (const auto& c : kWgradXsKernels)
-        if (c.Kb == b.Kb && c.parts == parts && c.wm == wm) k = &c;
-    if (!k) return fail(AP_ERR_UNSUPPORTED, "wgrad_xs: no kernel for k=%d, %d parts, %d wave rows", b.Kb, parts, wm);
+    const WgradXsKernel* k = xs_kernel(d, b);
+    if (!k)
+        return fail(AP_ERR_UNSUPPORTED, "wgrad_xs: no kernel for k=%d, %d parts, %d wave rows", b.Kb, d->precision == AP_PRECISION_BF16 ? 1 : 2,
+                    b.wide ? 4 : 2);
     rc = k->launch(p, (unsigned)(pl.m_tiles * b.c_tiles * pl.P), stream);
     if (rc) return rc;
     return launch_bf3_reduce(pl, d, workspace, dw, stream);

@@ -1082,6 +1082,21 @@ def wgrad_gt_dims(k, stride, pad, pad_mode, g_shape, srcs, precision=None):
     return tuple(dims)
 
 
+def wgrad_kernel_route(k, stride, pad, pad_mode, g, srcs, precision=None, own_g=True):
+    """What ap_conv2d_wgrad would launch for this layer, as ap_conv2d_wgrad_route words it: kernel table entry, operand forms, P and
+    nstages (a query: nothing is launched).  g, srcs: Feats or their forms; own_g False: the gradient comes prepared (g_t / g_xs)
+    and ``g`` only carries the shape.  For the tests, which state the kernel a case is meant to exercise; the product path does
+    not ask."""
+    g = form_of(g)
+    d = _wgrad_plan_desc(k, stride, pad, pad_mode, g.shape, [form_of(f) for f in srcs], precision)
+    if own_g:
+        stats = _SOME_POINTER if g.virtual else None
+        d.g = C.ApSrc(_SOME_POINTER, stats, stats, g.shape[1], g.act)
+    buf = ctypes.create_string_buffer(128)
+    C.check(C.lib().ap_conv2d_wgrad_route(ctypes.byref(d), buf, len(buf)), 'conv2d_wgrad_route')
+    return buf.value.decode()
+
+
 def pad_materialize(srcs, pad, pad_mode, hp=None, wp=None):
     """Padded, concatenated, normalised + activated copy of the (virtual) sources: (N, sum C, Hp, Wp)."""
     x0 = srcs[0].data

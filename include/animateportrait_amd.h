@@ -424,6 +424,18 @@ int64_t ap_conv2d_wgrad_workspace_floats(const ap_wgrad_desc* d);
 int ap_pad_materialize(const ap_src* src, int32_t nsrc, int32_t N, int32_t H, int32_t W, int32_t pad, int32_t pad_mode,
                        int32_t Hp, int32_t Wp, float* out, ap_stream_t stream);
 int ap_conv2d_wgrad(const ap_wgrad_desc* d, float* workspace, float* dw, ap_stream_t stream);
+/* What ap_conv2d_wgrad / _pre / _xs launch for a descriptor, as text built from the launcher's own plan (no device is touched, no
+ * pointer is followed): the descriptor's refusal code, else AP_OK and in buf
+ *   <kernel> g=<form> a=<form> P=<workgroups per tile> nstages=<pixel stages> [xs<Kb,parts,wave rows>]
+ * kernel: the table entry -- narrow<K,S,Cin,ppt> (ppt 1: the LDS-staged form), bf16gemm<Kb,split|heads|wide> (+s2d: the space-to-depth
+ * view of a stride-2 layer, +rows: the row view of a 7x7 stem), igemm<S,K,M_TILE,Q_TILE,PR>.  g / a: how the gradient and the
+ * shifted operand reach it -- general, vec, pad_rows, s2d_rows (the four split_transpose kernels), xs_transpose (re-tiled from the
+ * forward pass's split copies), pad (the fp32 kernel's padded copy), direct (read where it lies), none (d->g.data is NULL: the
+ * caller brings the operand, ap_conv2d_wgrad_pre / _xs).  xs<...>: ap_conv2d_wgrad_xs_ok holds, and this kernel of wgrad_xs.h
+ * serves ap_conv2d_wgrad_xs.  nstages is 0 for the narrow family.  Tests use it to state which kernel a layer exercises;
+ * ap_conv2d_wgrad_route_names lists every kernel table entry and operand form the text can name, one per line. */
+int ap_conv2d_wgrad_route(const ap_wgrad_desc* d, char* buf, int32_t buflen);
+int ap_conv2d_wgrad_route_names(char* buf, int32_t buflen);
 
 /* backward of a = act(InstanceNorm(y)) w.r.t. y.  The incoming gradient is fold(g1) + g2 where g1 has spatial
  * (H+2*g1_pad) x (W+2*g1_pad) (gradient of a reflection-padded consumer, nn.ReflectionPad2d backward fused) and g2
