@@ -1,4 +1,4 @@
-"""GPU (-m gpu): every kernel csrc/backward_elementwise.hip can launch for ap_instnorm_bwd, ap_act_bwd, ap_act_bwd_bias, ap_bias_grad
+"""GPU (-m gpu): every kernel csrc/instnorm_bwd.hip and csrc/act_bwd.hip can launch for ap_instnorm_bwd, ap_act_bwd, ap_act_bwd_bias, ap_bias_grad
 and ap_bias_grad_ws, against fp64 autograd / fp64 sums, at the shapes where the dispatch changes kernels.
 
 Each case states the route it is meant for and first asserts that ap_instnorm_bwd_route / ap_act_bwd_route name it, so the list

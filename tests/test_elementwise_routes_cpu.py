@@ -1,4 +1,4 @@
-"""CPU (-m "not gpu"): which kernel of csrc/backward_elementwise.hip a plane geometry takes, as ap_instnorm_bwd_route and
+"""CPU (-m "not gpu"): which kernel of csrc/instnorm_bwd.hip / csrc/act_bwd.hip a plane geometry takes, as ap_instnorm_bwd_route and
 ap_act_bwd_route state it -- the launchers switch on the same selectors.  Every boundary of the dispatch is walked with a shape on
 each side of it; tests/test_elementwise_bwd_gpu.py runs the kernels and states, per case, the route named here.  Also checked without
 a GPU: the refusals that need no launch, the slice counts of the two-stage bias gradient, that the GPU cases cover every route name,
