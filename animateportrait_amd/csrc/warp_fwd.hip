@@ -1,50 +1,25 @@
-// victim_product.hip -- library-free reproducer of the co-residency hazard, bisection of the VICTIM: the product's gather kernel
-// (animateportrait_amd/csrc/warp_fwd.hip, warp_concat_kernel, copied here) with pieces removed by -DKNOB=<n>, one object per n:
-//   0  verbatim                                   1  without the split-bf16 output paths (xs / s2d)
-//   2  ... and without the channel-octet input path 3  ... and without the partial-channel-group tail loop
-//   4  ... and without the `H == S` direct-read branch   5  ... and with the 32 x 8 tile as a constant (no run-time tw_shift)
-//   6  ... and without the null tests of x_mean / out
-// Built by the Makefile as victim_k<n>.o; launch_victim_k<n>() has the signature of launch_victim().
-#include <hip/hip_runtime.h>
-#include <cstdint>
+// warp_fwd.hip -- fused double_feature_warping (reference: Module2/models/networks.py:1298-1313 and
+// warp_acc_flow, Module2/intrinsic_flow_models/modules.py:596-625).
+//
+// One pass produces the 2C-channel concat the next convolution reads:
+//   out[:, 0:C ] = grid_sample(x, motion_L)                       bilinear / zeros / align_corners=False
+//   out[:, C:2C] = where(mask_L > 0.5, grid_sample(x, grid(flow_L)), -1)
+// motion_L, flow_L, mask_L are the align_corners=True bilinear resizes of the full-resolution inputs
+// to the feature resolution, evaluated per output pixel instead of being materialised, and x may be a
+// raw conv output whose InstanceNorm+ReLU is applied per gathered tap.
+//
+// HBM-bound gather: one lane per output pixel (consecutive lanes = consecutive x, so the two stores
+// per channel are coalesced 256-B rows); sample coordinates and the 2x4 tap offsets/weights are
+// computed once per pixel and reused for CG channels.
+//
+// The backward scatter is warp_bwd.hip; this translation unit is the one the co-residency lab rebuilds
+// (tools/hazard/build_victims.sh, tools/hazard/repro).
+#include "warp_sample.h"
+#include <climits>
+#include <cstring>
 #include <type_traits>
-#ifndef KNOB
-#define KNOB 0
-#endif
-#define CAT_(a, b) a##b
-#define CAT(a, b) CAT_(a, b)
-namespace CAT(vk, KNOB) {
-__device__ __forceinline__ unsigned xcd_logical_block(unsigned nblk, unsigned b) {
-    const unsigned q = nblk >> 3, r = nblk & 7, xcd = b & 7, idx = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-struct Taps {
-    int off[4];     // offset inside a channel plane, or -1 when the tap is out of range (contributes 0)
-    float w[4];
-};
 
-__device__ __forceinline__ Taps make_taps(float gx, float gy, int H, int W) {
-    // grid_sampler_unnormalize, align_corners=False: ((g + 1) * size - 1) / 2
-    float ix = ((gx + 1.f) * (float)W - 1.f) / 2.f;
-    float iy = ((gy + 1.f) * (float)H - 1.f) / 2.f;
-    ix = fminf(fmaxf(ix, -2.f), (float)W + 1.f);   // everything beyond is all-zero taps anyway
-    iy = fminf(fmaxf(iy, -2.f), (float)H + 1.f);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    const float ex = fx + 1.f, ey = fy + 1.f;
-    Taps t;
-    t.w[0] = (ex - ix) * (ey - iy);   // nw
-    t.w[1] = (ix - fx) * (ey - iy);   // ne
-    t.w[2] = (ex - ix) * (iy - fy);   // sw
-    t.w[3] = (ix - fx) * (iy - fy);   // se
-    const bool xin0 = x0 >= 0 && x0 < W, xin1 = x1 >= 0 && x1 < W;
-    const bool yin0 = y0 >= 0 && y0 < H, yin1 = y1 >= 0 && y1 < H;
-    t.off[0] = (xin0 && yin0) ? y0 * W + x0 : -1;
-    t.off[1] = (xin1 && yin0) ? y0 * W + x1 : -1;
-    t.off[2] = (xin0 && yin1) ? y1 * W + x0 : -1;
-    t.off[3] = (xin1 && yin1) ? y1 * W + x1 : -1;
-    return t;
-}
+namespace apamd {
 
 // north-west corner of a sample (the clamped floor make_taps uses): what the quad-cooperative gather addresses rows by
 __device__ __forceinline__ void tap_corner(float gx, float gy, int H, int W, int& x0, int& y0) {
@@ -56,25 +31,6 @@ __device__ __forceinline__ void tap_corner(float gx, float gy, int H, int W, int
     y0 = (int)floorf(iy);
 }
 
-struct Lerp { int i0, i1; float l0, l1; };
-
-// F.interpolate(mode='bilinear', align_corners=True): src = dst * (S-1)/(H-1)
-__device__ __forceinline__ Lerp make_lerp(int dst, int S, int H) {
-    const float scale = H > 1 ? (float)(S - 1) / (float)(H - 1) : 0.f;
-    const float src = scale * (float)dst;
-    Lerp l;
-    l.i0 = (int)src;
-    if (l.i0 > S - 1) l.i0 = S - 1;
-    l.i1 = l.i0 + (l.i0 < S - 1 ? 1 : 0);
-    l.l1 = src - (float)l.i0;
-    l.l0 = 1.f - l.l1;
-    return l;
-}
-
-__device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v11, const Lerp& ly, const Lerp& lx) {
-    return ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11);
-}
-
 __device__ __forceinline__ float tap_val(const float* plane, int off, float m, float r, int act) {
     if (off < 0) return 0.f;
     float v = (plane[off] - m) * r;
@@ -82,8 +38,6 @@ __device__ __forceinline__ float tap_val(const float* plane, int off, float m, f
     else if (act == 2) v = v > 0.f ? v : 0.2f * v;
     return v;
 }
-
-constexpr int kWarpCG = 8;   // channels per thread = one 16-byte slot of the split-bf16 layout
 
 typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
 
@@ -141,6 +95,18 @@ __device__ __forceinline__ void store_split_slot_s2d(uint4* xs, int n, int CG2, 
         for (int r = 0; r < 4; ++r) { plane(0, r >> 1, r & 1)[HW2] = z; plane(1, r >> 1, r & 1)[HW2] = z; }
     }
 }
+
+// grid: (ceil(H*W/256), ceil(C/CG), N).  out (fp32 [N, 2C, H, W]) and xs (its split-bf16 copy) are both optional.
+// ACT (= x_act) is a template parameter: with a run-time activation the compiler evaluated ReLU AND LeakyReLU for every
+// one of the 64 gathered values and selected (12 vector instructions per value; the kernel is as much VALU- as memory-bound).
+// GATHER = 1 (tools / A-B runs only, APAMD_WARP_GATHER=quad): the "wavefront-shuffle" gather BASELINE.json names, in its cheapest
+// form for the channel-octet layout -- the four lanes of a quad fetch each other's 64-byte tap-row segments (two neighbouring
+// pixels x 8 channels) as ONE contiguous request per member and row, then transpose the 4 x 4 x 16-byte block inside the quad
+// with DPP quad_perm exchanges: a quarter of the L1 requests of the lane-per-pixel gather for ~200 more vector instructions per
+// pixel.  Measured slower (profiles/r04_warp_variants.md); kept so that the rejection has its measurement.
+#ifndef APAMD_WARP_WPE
+#define APAMD_WARP_WPE 4
+#endif
 template <int ACT, int WPE, int GATHER = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void warp_concat_kernel(const float* __restrict__ x, const float* __restrict__ x_mean,
                                                           const float* __restrict__ x_rstd, int x_act,
@@ -164,27 +130,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         by = t % gridDim.y;
         bz = t / gridDim.y;
     }
-#if KNOB < 1
     if (xs != nullptr && !s2d && bx == 0 && threadIdx.x < 4) {
         // the all-zero slot that closes every plane of the split layout (this block's two channel groups x 2 parts)
         const int CG2 = (2 * C) >> 3, HWz = H * W;
         const int part = threadIdx.x & 1, cg = (threadIdx.x >> 1) ? (C >> 3) + by : by;
         xs[((long long)(bz * 2 + part) * CG2 + cg) * (HWz + 1) + HWz] = make_uint4(0u, 0u, 0u, 0u);
     }
-#endif
     // a workgroup covers a tw x (256 / tw) pixel tile when the map divides into such tiles (tw_shift > 0), else 256
     // consecutive pixels: the taps of a compact tile fall into a window the CU's L1 holds, those of a 256-pixel row
     // segment (16 noisy rows high) do not -- the gathers are then served line by line from the L2
     int pix, oy, ox;
-#if KNOB >= 5
-    {
-        const int tiles_x = W >> 5;
-        const int ty = bx / tiles_x, tx = bx - ty * tiles_x;
-        oy = ty * 8 + ((int)threadIdx.x >> 5);
-        ox = (tx << 5) + ((int)threadIdx.x & 31);
-        pix = oy * W + ox;
-    }
-#else
     if (tw_shift > 0) {
         const int tiles_x = W >> tw_shift;
         const int ty = bx / tiles_x, tx = bx - ty * tiles_x;
@@ -197,12 +152,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         oy = pix / W;
         ox = pix - oy * W;
     }
-#endif
     const int n = bz;
     const long long SS = (long long)S * S;
 
     float gx, gy, fx, fy, mk;
-    if (KNOB < 4 && H == S && W == S) {
+    if (H == S && W == S) {
         const float2 g = reinterpret_cast<const float2*>(motion)[n * SS + pix];
         gx = g.x; gy = g.y;
         fx = flow[(n * 2 + 0) * SS + pix] * flow_scale;
@@ -250,7 +204,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         }
         float v1[8], v2[8];
         float a[8][4], b[8][4], m[8], r[8];
-        if (KNOB < 2 && xoct) {
+        if (xoct) {
             // a tap is the 32 contiguous bytes of the group's 8 channels: two 16-byte loads instead of 8 dword gathers
             // from 8 planes (the NCHW form is bound by the L1's line rate: every lane's tap is its own line per channel)
             const float4* og = reinterpret_cast<const float4*>(x + ((long long)n * (C >> 3) + by) * HW * 8);
@@ -316,7 +270,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         for (int c = 0; c < 8; ++c) {
             const float* plane = x + ((long long)n * C + c0 + c) * HW;
             m[c] = 0.f; r[c] = 1.f;
-            if (KNOB >= 6 || x_mean != nullptr) { m[c] = x_mean[n * C + c0 + c]; r[c] = x_rstd[n * C + c0 + c]; }
+            if (x_mean != nullptr) { m[c] = x_mean[n * C + c0 + c]; r[c] = x_rstd[n * C + c0 + c]; }
 #pragma unroll
             for (int k = 0; k < 4; ++k) { a[c][k] = plane[om[k]]; b[c][k] = plane[of[k]]; }
         }
@@ -344,14 +298,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             v1[c] = s1.x; v1[c + 1] = s1.y;
             v2[c] = keep ? s2.x : -1.f; v2[c + 1] = keep ? s2.y : -1.f;
         }
-        if (KNOB >= 6 || out != nullptr) {
+        if (out != nullptr) {
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 out[((long long)n * 2 * C + c0 + c) * HW + pix] = v1[c];
                 out[((long long)n * 2 * C + C + c0 + c) * HW + pix] = v2[c];
             }
         }
-#if KNOB < 1
         if (xs != nullptr && s2d) {
             store_split_slot_s2d(xs, n, (2 * C) >> 3, by, H, W, oy, ox, v1);
             store_split_slot_s2d(xs, n, (2 * C) >> 3, (C >> 3) + by, H, W, oy, ox, v2);
@@ -359,10 +312,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             store_split_slot(xs, n, (2 * C) >> 3, by, HW, pix, v1);
             store_split_slot(xs, n, (2 * C) >> 3, (C >> 3) + by, HW, pix, v2);
         }
-#endif
         return;
     }
-    if (KNOB >= 3) return;
     for (int c = c0; c < c1; ++c) {
         const float* plane = x + ((long long)n * C + c) * HW;
         float m = 0.f, r = 1.f;
@@ -380,11 +331,73 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         out[((long long)n * 2 * C + C + c) * HW + pix] = v2;
     }
 }
-}  // namespace
-extern "C" hipError_t CAT(launch_victim_k, KNOB)(const float* x, const float* mean, const float* rstd, const float* motion, const float* flow,
-                                                  const float* ifmask, float* out, int N, int C, int H, int W, int S, float flow_scale, hipStream_t stream) {
-    dim3 grid((H * W + 255) / 256, (C + 7) / 8, N);
-    hipLaunchKernelGGL((CAT(vk, KNOB)::warp_concat_kernel<1, 4, 0>), grid, dim3(256), 0, stream, x, mean, rstd, 1, motion, flow, ifmask, out,
-                       (uint4*)nullptr, C, H, W, S, flow_scale, 0, 5);
-    return hipGetLastError();
+
+// The instantiations the library serves, [gather][x_act].
+// (WPE = 4: 112 registers, no spills.  A budget for 5 waves per SIMD -- 96 registers, a dozen spills -- measured 210 us
+// against 154 us at the 256^2 level.)
+// (APAMD_WARP_WPE: victim-side variants of the co-residency lab, tools/hazard/build_victims.sh; the product builds 4)
+using WarpFwdKernel = decltype(&warp_concat_kernel<0, APAMD_WARP_WPE>);
+static const WarpFwdKernel kWarpFwdKernels[2][3] = {
+    {warp_concat_kernel<0, APAMD_WARP_WPE>, warp_concat_kernel<1, APAMD_WARP_WPE>, warp_concat_kernel<2, APAMD_WARP_WPE>},
+    {warp_concat_kernel<0, APAMD_WARP_WPE, 1>, warp_concat_kernel<1, APAMD_WARP_WPE, 1>, warp_concat_kernel<2, APAMD_WARP_WPE, 1>},
+};
+
+// A/B switch for tools/warp_fwd_bench.py: the quad-cooperative gather (channel-octet inputs, whole 256-pixel blocks of
+// 4-aligned rows, so that every quad is four live neighbours of one row)
+static bool quad_gather_route(int flags, int H, int W) {
+    const char* gather = getenv("APAMD_WARP_GATHER");           // read per call: tests flip it inside one process
+    const bool quad = gather && !strcmp(gather, "quad");
+    return quad && (flags & 2) && (W & 3) == 0 && W >= 4 && ((H * W) & 255) == 0;
+}
+
+// tile width (log2): 32 x 8 pixels when the map divides into them (APAMD_WARP_TILE = 0 / 4 / 5 / 6 for A/B runs, read once
+// per process), 0 = 256 consecutive pixels when it does not
+static int warp_tile_shift(int H, int W) {
+    static const int tile_env = env_int("APAMD_WARP_TILE", 5);
+    if (tile_env < 4 || tile_env > 6 || (W & ((1 << tile_env) - 1)) || (H & ((256 >> tile_env) - 1))) return 0;
+    return tile_env;
+}
+
+}  // namespace apamd
+
+using namespace apamd;
+
+extern "C" int ap_warp_concat_fwd_ex(const float* x, const float* x_mean, const float* x_rstd, int32_t x_act,
+                                     const float* motion, const float* flow, const float* ifmask, float* out,
+                                     void* xs, int32_t N, int32_t C, int32_t H, int32_t W, int32_t S,
+                                     float flow_scale, int32_t flags, ap_stream_t stream) {
+    const int s2d = flags & 1;
+    if ((flags & 2) && (C % kWarpCG) != 0)
+        return fail(AP_ERR_INVALID, "warp_concat_fwd: the channel-octet input layout needs C %% 8 == 0");
+    if (s2d && (!xs || (H & 1) || (W & 1) || (C % kWarpCG) != 0))
+        return fail(AP_ERR_INVALID, "warp_concat_fwd: the space-to-depth split output needs xs, an even map and C %% 8 == 0");
+    if (!x || !motion || !flow || !ifmask) return fail(AP_ERR_INVALID, "warp_concat_fwd: null pointer");
+    if (!out && !xs) return fail(AP_ERR_INVALID, "warp_concat_fwd: neither an fp32 nor a split output");
+    if ((x_mean == nullptr) != (x_rstd == nullptr)) return fail(AP_ERR_INVALID, "warp_concat_fwd: mean/rstd mismatch");
+    if (N < 1 || C < 1 || H < 1 || W < 1 || S < 1) return fail(AP_ERR_INVALID, "warp_concat_fwd: bad sizes");
+    if (x_act < 0 || x_act > 2) return fail(AP_ERR_INVALID, "warp_concat_fwd: act %d", x_act);
+    if (N > 65535) return fail(AP_ERR_UNSUPPORTED, "warp_concat_fwd: N too large");
+    if ((long long)H * W > INT_MAX / 2)      // pixel and tap offsets inside a plane are ints
+        return fail(AP_ERR_UNSUPPORTED, "warp_concat_fwd: H * W <= %d is served (got %d x %d)", INT_MAX / 2, H, W);
+    if ((C % kWarpCG) != 0 && (xs || !out))
+        return fail(AP_ERR_UNSUPPORTED, "warp_concat_fwd: the split output needs C %% 8 == 0 (C=%d)", C);
+    hipLaunchKernelGGL(kWarpFwdKernels[quad_gather_route(flags, H, W)][x_act], warp_grid((H * W + 255) / 256, C, N), dim3(256), 0,
+                       (hipStream_t)stream, x, x_mean, x_rstd, x_act, motion, flow, ifmask, out, reinterpret_cast<uint4*>(xs),
+                       C, H, W, S, flow_scale, flags & 3, warp_tile_shift(H, W));
+    return check_launch("warp_concat_kernel");
+}
+
+extern "C" int ap_warp_concat_fwd_split(const float* x, const float* x_mean, const float* x_rstd, int32_t x_act,
+                                        const float* motion, const float* flow, const float* ifmask, float* out,
+                                        void* xs, int32_t N, int32_t C, int32_t H, int32_t W, int32_t S,
+                                        float flow_scale, ap_stream_t stream) {
+    return ap_warp_concat_fwd_ex(x, x_mean, x_rstd, x_act, motion, flow, ifmask, out, xs, N, C, H, W, S, flow_scale, 0, stream);
+}
+
+extern "C" int ap_warp_concat_fwd(const float* x, const float* x_mean, const float* x_rstd, int32_t x_act,
+                                  const float* motion, const float* flow, const float* ifmask, float* out, int32_t N,
+                                  int32_t C, int32_t H, int32_t W, int32_t S, float flow_scale, ap_stream_t stream) {
+    if (!out) return fail(AP_ERR_INVALID, "warp_concat_fwd: null pointer");
+    return ap_warp_concat_fwd_split(x, x_mean, x_rstd, x_act, motion, flow, ifmask, out, nullptr, N, C, H, W, S,
+                                    flow_scale, stream);
 }

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the kernels outside the convolution files -- the LSTM recurrence (csrc/lstm.hip), the spline solve and warp and the
-fused Adam (csrc/tps.hip), resize / grid_sample / pixel_shuffle (csrc/warp.hip) -- at the edges of their C contracts, each against a
+fused Adam (csrc/tps.hip), resize / grid_sample / pixel_shuffle (csrc/image_ops.hip) -- at the edges of their C contracts, each against a
 float64 evaluation of the same operation on the CPU.
 
 Every output is a window inside a larger buffer filled with a sentinel; the sentinel has to survive around the window (and, for the

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the feature-warp kernels of csrc/warp.hip -- warp_concat_kernel (forward gather: four layouts, three activations, two
+"""GPU (-m gpu): the feature-warp kernels of csrc/warp_fwd.hip and csrc/warp_bwd.hip -- warp_concat_kernel (forward gather: four layouts, three activations, two
 pixel-to-thread mappings), warp_concat_bwd_tiled_kernel (LDS-window scatter) and warp_concat_bwd_kernel (APAMD_WARP_BWD_PLAIN=1) --
 held to the C contract "any N, C, H, W, S >= 1" at ragged, degenerate and non-square shapes and on hostile sampling maps, each
 against the float64 reference of tests/warp_reference.py.

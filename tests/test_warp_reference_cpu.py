@@ -54,7 +54,7 @@ def test_excluded_share_stays_under_the_cap(label, kind, shape, seed):
 
 
 def test_box_model_has_the_kernels_constants():
-    src = open(os.path.join(ROOT, 'animateportrait_amd', 'csrc', 'warp.hip')).read()
+    src = open(os.path.join(ROOT, 'animateportrait_amd', 'csrc', 'warp_bwd.hip')).read()
 
     def const(name):
         return int(re.search(r'\b%s = (\d+)' % name, src).group(1))

@@ -1,4 +1,4 @@
-"""Reference of the feature-warp kernels (csrc/warp.hip) for ANY N, C, H, W, S -- a plain helper module of the tests, CPU only.
+"""Reference of the feature-warp kernels (csrc/warp_fwd.hip, csrc/warp_bwd.hip) for ANY N, C, H, W, S -- a plain helper module of the tests, CPU only.
 
 ``warp_concat_ref`` restates double_feature_warping (oracle/warp.py, which is tied to 256 / 128 / 64) with the same torch calls on
 independent H, W and S; its backward is torch autograd through it.  Evaluated in float64 it is what the kernels are compared with,
@@ -15,7 +15,7 @@ import torch.nn.functional as F
 
 MAX_EXCLUDED = 0.005          # a case may exclude at most this share of its pixels as ambiguous (asserted, not measured)
 
-# geometry of warp_concat_bwd_tiled_kernel (csrc/warp.hip: kBwdTileW, kBwdTileH, kBwdWin, kBwdWinW)
+# geometry of warp_concat_bwd_tiled_kernel (csrc/warp_bwd.hip: kBwdTileW, kBwdTileH, kBwdWin, kBwdWinW)
 TILE_W, TILE_H, WIN, WIN_W = 32, 16, 1344, 48
 
 

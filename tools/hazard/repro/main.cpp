@@ -26,7 +26,7 @@ extern "C" hipError_t launch_victim(int level, const float* x, const float* mean
 extern "C" size_t victim_out_floats(int level, int N, int C, int H, int W);
 extern "C" hipError_t launch_count_diff(const void* a, const void* ref, size_t n_words, unsigned long long* count, unsigned* lane_hist, hipStream_t stream);
 
-// LEVEL 3 = the product's own translation unit (animateportrait_amd/csrc/warp.hip compiled into this program, `make PRODUCT=1`
+// LEVEL 3 = the product's own translation unit (animateportrait_amd/csrc/warp_fwd.hip compiled into this program, `make PRODUCT=1`
 // is the default): the kernel that fails in the lab, through its C entry point.  Its two external helpers are defined here.
 extern "C" int ap_warp_concat_fwd_ex(const float* x, const float* x_mean, const float* x_rstd, int32_t x_act, const float* motion, const float* flow,
                                      const float* ifmask, float* out, void* xs, int32_t N, int32_t C, int32_t H, int32_t W, int32_t S,
