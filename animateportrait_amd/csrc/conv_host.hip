@@ -6,6 +6,7 @@
 #include "common.h"
 #include "conv_registry.h"
 #include "conv_direct.h"
+#include "conv_tapgemm.h"
 #include "conv_bf3_registry.h"
 #include "conv_prepass.h"
 #include "conv_small.h"
@@ -883,7 +884,41 @@ static int launch_small(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a)
     return check_launch("conv_small_f32");
 }
 
+// The generator's output layer in split-bf16 arithmetic -- one reflection-padded 64-channel source, one output channel, no
+// statistics epilogue -- multiplies on the matrix pipe (conv_tapgemm.h).  Same plan, same packed image: chosen here, at launch.
+static bool tapgemm_serves(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+    return d->precision == AP_PRECISION_BF16X3 && d->Cout == 1 && d->KH == 7 && d->nsrc == 1 && d->src[0].C == TapGemmCfg::C &&
+           d->pad_mode == AP_PAD_REFLECT && !a.stats && pl.cin_pad == TapGemmCfg::C;
+}
+
+// Tile height: the workgroups (two per CU) run in rounds, and a workgroup stages th + 6 rows for th output rows
+static int launch_tapgemm(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+    const void* kfn = tapgemm_kernel();
+    int rc = ensure_dyn_lds(kfn, 160 * 1024);
+    if (rc) return rc;
+    TapGemmParams p;
+    memset(&p, 0, sizeof(p));
+    fill_seg(p.seg, d->src[0], 0);
+    p.N = d->N; p.H = d->H; p.W = d->W;
+    p.y = a.y; p.wp = a.packed; p.bias = a.bias; p.act = d->act;
+    p.tiles_x = (pl.Wout + TapGemmCfg::TW - 1) / TapGemmCfg::TW;
+    const long long slots = 2LL * num_cus();
+    long long best_cost = -1;
+    for (int ty = 1; ty <= (pl.Hout + 7) / 8; ++ty) {
+        const int th = (pl.Hout + ty - 1) / ty;
+        const long long wgs = (long long)d->N * p.tiles_x * ((pl.Hout + th - 1) / th);
+        const long long cost = ((wgs + slots - 1) / slots) * (th + 6);
+        if (best_cost < 0 || cost < best_cost) { p.th = th; best_cost = cost; }
+    }
+    p.tiles_y = (pl.Hout + p.th - 1) / p.th;
+    void* args[] = {&p};
+    hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)(d->N * p.tiles_y * p.tiles_x)), dim3(256), args, TapGemmCfg::lds_bytes(), a.stream);
+    if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "conv_tapgemm_bf16x3 launch: %s", hipGetErrorString(e));
+    return AP_OK;
+}
+
 static int launch_direct(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+    if (tapgemm_serves(d, pl, a)) return launch_tapgemm(d, pl, a);
     const void* kfn = direct_fn(d->KH, pl.direct_cop);
     int rc = ensure_dyn_lds(kfn, 160 * 1024);
     if (rc) return rc;
