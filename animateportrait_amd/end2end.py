@@ -115,6 +115,9 @@ def make_parser():
     ap.add_argument('--max_frames', type=int, default=None)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--size', type=int, default=256)
+    ap.add_argument('--style', choices=('drawing', 'cartoon'), default='drawing',
+                    help='cartoon: the model options of the cartoon experiment (--name formal/cartoon --output_nc 3, '
+                         'main_end2end_module2.py:100-103; both can still be given explicitly); frames have three channels')
     ap.add_argument('--triangulate', choices=('host', 'device'), default='host',
                     help='where the motion grids\' Delaunay triangulation runs: scipy on the CPU per frame, or ap_delaunay on the GPU '
                          '(the landmark sequence is then uploaded once and no per-frame work is left on the host)')
@@ -281,7 +284,12 @@ def main(argv=None, prepare_model=None):
     # the model's own options: the test settings of test_gan_new (:95-104) unless given
     defaults = ['--model', 'geomcgt_ifw_test', '--netG', 'resnet_9blocks_rcatland32_full_ifw', '--netg_resb_div', '3',
                 '--netg_resb_disp', '3', '--output_nc', '1', '--dataset_mode', 'synthetic', '--blendbg', '1', '--gpu_ids', '0']
+    if a.style == 'cartoon':
+        # the model takes the cartoon branch for experiment names that contain 'cartoon' (geomcgt_ifw_test_model.py:228)
+        defaults += ['--output_nc', '3', '--name', 'formal/cartoon']          # (argparse keeps the last value of an option)
     opt = TestOptions().parse(defaults + rest)
+    if a.style == 'cartoon' and 'cartoon' not in opt.name:
+        ap.error('--style cartoon with --name %s: the cartoon branch is selected by an experiment name that contains "cartoon"' % opt.name)
     torch.cuda.set_device(opt.gpu_ids[0])
     model = create_model(opt)
     if prepare_model is not None:

@@ -15,7 +15,13 @@ What is different (and why):
 * The static drawing depends on the photo only, and the photo is constant over a clip: it is computed once per
   distinct ``real_A`` tensor and cached, where the reference recomputes it per frame.
 * Batched: every formula is applied per sample (the reference is written for batch size 1).
-* The 'cartoon' branch needs the third-party Photo2Cartoon checkpoint and is outside the path.
+* Experiment names that contain 'cartoon' (:228-229, 286-291): the reference round-trips the photo through uint8 and calls
+  ``Photo2Cartoon.inference2(img, nocrop=1)`` (photo2cartoon.py:569-600).  On that branch the segmentation mask is computed
+  and never applied, the 256 -> 256 resize is the identity and nothing is cropped or detected, so the static cartoon is
+  exactly ``ResnetGenerator(ngf=32, img_size=256, light=True)(q(real_A))[0]`` with ``q`` the uint8 round trip
+  ``floor((x + 1) 127.5) / 127.5 - 1`` -- networks.Photo2CartoonGenerator, loaded from ``checkpoints/static/cartoon.pt``
+  (key ``genA2B``).  No TensorFlow, dlib or face_alignment is involved.  The input contract is [-1, 1]: a value outside is
+  clamped to the byte range, where numpy's cast would wrap it.  Per sample, where the reference reads ``real_A[0]``.
 """
 import torch
 
@@ -45,12 +51,15 @@ class GeomCGTIFWTestModel(BaseModel):
                                         opt.init_type, opt.init_gain, gid, div=opt.netg_resb_div,
                                         disp=opt.netg_resb_disp)                   # :211-213
         self.aux = {'modnet': None, 'netF': None}
-        if 'cartoon' in opt.name:
-            raise NotImplementedError('the cartoon branch needs the third-party Photo2Cartoon checkpoint '
-                                      '(geomcgt_ifw_test_model.py:228-229) and is outside the MI355X hot path')
-        # 'drawing' (the README / main_end2end configuration): static generator, frozen           :224-227
-        self.net_staticG = networks.define_G(3, 1, 64, 'resnet_style2_9blocks', 'instance', use_dropout=False,
-                                             gpu_ids=gid)
+        self.cartoon = 'cartoon' in opt.name
+        if self.cartoon:
+            # the static cartoon generator of the Photo2Cartoon project, frozen                        :228-229
+            self.net_staticG = networks.Photo2CartoonGenerator(ngf=32, img_size=256, light=True).to(self.device)
+            self.STATIC_CHECKPOINT = 'checkpoints/static/cartoon.pt'
+        else:
+            # 'drawing' (the README / main_end2end configuration): static generator, frozen           :224-227
+            self.net_staticG = networks.define_G(3, 1, 64, 'resnet_style2_9blocks', 'instance', use_dropout=False,
+                                                 gpu_ids=gid)
         self.net_staticG.eval()
         self._static_key = None
         self._style = None
@@ -66,15 +75,20 @@ class GeomCGTIFWTestModel(BaseModel):
             if os.path.exists(self.STATIC_CHECKPOINT):
                 self.load_static(self.STATIC_CHECKPOINT)
             elif not getattr(opt, 'allow_random_init', False):
-                raise FileNotFoundError('%s (static drawing generator) not found; load it with load_static(path) '
-                                        'before setup() or pass --allow_random_init' % self.STATIC_CHECKPOINT)
+                raise FileNotFoundError('%s (static %s generator) not found; load it with load_static(path) '
+                                        'before setup() or pass --allow_random_init'
+                                        % (self.STATIC_CHECKPOINT, 'cartoon' if self.cartoon else 'drawing'))
             else:
-                print('WARNING: --allow_random_init: static drawing generator runs with RANDOM weights')
+                print('WARNING: --allow_random_init: static %s generator runs with RANDOM weights'
+                      % ('cartoon' if self.cartoon else 'drawing'))
         BaseModel.setup(self, opt)
 
     def load_static(self, path):
-        """checkpoints/static/drawing.pth (:226): same key names, strict."""
+        """checkpoints/static/drawing.pth (:226), or checkpoints/static/cartoon.pt's ``genA2B`` entry (:229,
+        photo2cartoon.py:534-535): same key names, strict."""
         sd = torch.load(path, map_location=self.device)
+        if self.cartoon:
+            sd = sd['genA2B']
         self.net_staticG.load_state_dict(sd, strict=True)
         self._static_key = None
         self._static_loaded = True
@@ -119,9 +133,15 @@ class GeomCGTIFWTestModel(BaseModel):
 
     # ------------------------------------------------------------------------------------------------ forward
     def static_drawing(self, real_A):
-        """:280-285, cached per photo: style planes (0, 1, 0) at 128^2, 256 -> 512 -> G_static -> 256."""
+        """:280-291, cached per photo.  Drawing: style planes (0, 1, 0) at 128^2, 256 -> 512 -> G_static -> 256.
+        Cartoon: the unmasked photo through the uint8 round trip, G_static at 256^2, (N, 3, 256, 256)."""
         key = self._photo_key
-        if self._static_key != key:
+        if self._static_key != key and self.cartoon:
+            # :286-291 with inference2(nocrop=1) reduced to what it computes: G(q(photo)) at 256^2, the tanh image as it is
+            from .. import style_ops
+            self.fakeB_static = self.net_staticG(style_ops.quantize_u8(real_A).contiguous())
+            self._static_key = key
+        elif self._static_key != key:
             n = real_A.shape[0]
             if self._style is None or self._style.shape[0] != n:
                 self._style = torch.tensor([0., 1., 0.], device=real_A.device).view(1, 3, 1, 1).repeat(n, 1, 128, 128)

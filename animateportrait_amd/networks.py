@@ -341,6 +341,267 @@ class ResnetStyle2Generator(nn.Module):
             return cf(None, self.model[str(j + 7)], x, act=ACT_TANH).data
 
 
+# --------------------------------------------------------------------------- Photo2Cartoon (static cartoon generator)
+class P2CConv(ConvLayer):
+    """One nn.Conv2d of Module2/models/photo2cartoon.py: as ConvLayer, but most of that file's convolutions have no bias
+    (then ``bias`` is not a state_dict key), and every one of them goes through ops.conv2d as it is; the instance norm +
+    activation of its source is fused into its loads by the Feat it is handed.
+
+    Arithmetic: exact fp32 whatever the package's default precision.  The generator is some 130 normalised layers deep, and
+    an operand error of 2^-17 injected early is amplified past the 1e-3 budget on the way: measured at ngf 32, 256 x 256
+    against float64, L-inf 2.7e-3 with the split-bf16 kernels where they apply (1.1e-3 with only the 7x7 stem in fp32) and
+    2.5e-4 in fp32 -- what stock fp32 operators give (2.4e-4).  The forward takes 10.5 ms either way: it is bound by its
+    several hundred launches, not by the matrix pipe, and runs once per photo."""
+
+    def __init__(self, cin, cout, k, stride=1, pad=0, pad_mode=PAD_ZERO, bias=False):
+        super().__init__([cin], cout, k, stride, pad, pad_mode)
+        self.spec.precision = ops.PRECISION_FP32
+        nn.init.normal_(self.weight.data, 0.0, 0.02)
+        if not bias:
+            self.register_parameter('bias', None)
+
+    def run(self, src, norm_act=None, act=ACT_NONE):
+        """norm_act=None: act(conv [+ bias]), a plain Feat.  norm_act=ACT_*: the raw output with its InstanceNorm statistics,
+        to be read as norm_act(IN(raw)) by the consumer."""
+        if norm_act is None:
+            return ops.conv2d(self.spec, [src], self.packed(), None if self.bias is None else self.bias.detach(), act=act)
+        return ops.conv2d(self.spec, [src], self.packed(), None, want_stats=True, out_act=norm_act)
+
+
+def _in_relu(t):
+    """(y, mean, rstd) of a style_ops producer -> the Feat that its consumers read as relu(IN(y)); ``.data`` stays plain y."""
+    return Feat(t[0], t[1], t[2], ACT_RELU)
+
+
+class P2CConvBlock(nn.Module):
+    """photo2cartoon.py:293-328: x -> residual + cat(x1, x2, x3), every convolution behind InstanceNorm + ReLU."""
+
+    def __init__(self, dim_in, dim_out):
+        super().__init__()
+        self.dim_in, self.dim_out = dim_in, dim_out
+        self.ConvBlock1 = _seq(_3=P2CConv(dim_in, dim_out // 2, 3, 1, 1, PAD_REFLECT))
+        self.ConvBlock2 = _seq(_3=P2CConv(dim_out // 2, dim_out // 4, 3, 1, 1, PAD_REFLECT))
+        self.ConvBlock3 = _seq(_3=P2CConv(dim_out // 4, dim_out // 4, 3, 1, 1, PAD_REFLECT))
+        self.ConvBlock4 = _seq(_2=P2CConv(dim_in, dim_out, 1))
+
+    def run(self, f, want_stats):
+        """f: relu(IN(.)) view of the plain input (see _in_relu).  The result is plain; want_stats: with its statistics."""
+        from . import style_ops as so
+        x1 = self.ConvBlock1['3'].run(f, norm_act=ACT_RELU)
+        x2 = self.ConvBlock2['3'].run(x1, norm_act=ACT_RELU)
+        x3 = self.ConvBlock3['3'].run(x2)
+        r = f.data if self.dim_in == self.dim_out else self.ConvBlock4['2'].run(f).data
+        out = so.join(r, x1.data, x2.data, x3.data, want_stats)
+        return _in_relu(out) if want_stats else Feat(out)
+
+
+class P2CHourGlassBlock(nn.Module):
+    """photo2cartoon.py:360-415: four levels of ConvBlock / avg_pool2d down, nearest up-sampling + skip back up."""
+
+    def __init__(self, dim_in, dim_out):
+        super().__init__()
+        for name in ('1_1', '1_2', '2_1', '2_2', '3_1', '3_2', '4_1', '4_2', '5', '6', '7', '8', '9'):
+            setattr(self, 'ConvBlock' + name, P2CConvBlock(dim_in if name == '1_1' else dim_out, dim_out))
+
+    def run(self, x):
+        from . import style_ops as so
+        skips, down = [], x
+        for lvl in '1234':
+            skips.append(getattr(self, 'ConvBlock%s_1' % lvl).run(down, False))
+            down = getattr(self, 'ConvBlock%s_2' % lvl).run(_in_relu(so.pool2(down.data, True)), True)
+        up = self.ConvBlock5.run(down, True)
+        for name, skip in zip('6789', reversed(skips)):
+            up = _in_relu(so.up2_add(getattr(self, 'ConvBlock' + name).run(up, False).data, skip.data, True))
+        return up
+
+
+class P2CHourGlass(nn.Module):
+    """photo2cartoon.py:330-357."""
+
+    def __init__(self, dim_in, dim_out, use_res=True):
+        super().__init__()
+        self.use_res = use_res
+        self.HG = _seq(_0=P2CHourGlassBlock(dim_in, dim_out), _1=P2CConvBlock(dim_out, dim_out), _2=P2CConv(dim_out, dim_out, 1))
+        self.Conv1 = P2CConv(dim_out, 3, 1, bias=True)
+        if use_res:
+            self.Conv2 = P2CConv(dim_out, dim_out, 1, bias=True)
+            self.Conv3 = P2CConv(3, dim_out, 1, bias=True)
+
+    def run(self, x, want_stats=False):
+        from . import style_ops as so
+        ll = self.HG['1'].run(self.HG['0'].run(x), False)
+        ll = self.HG['2'].run(ll, norm_act=ACT_RELU)
+        tmp_out = self.Conv1.run(ll)
+        if not self.use_res:
+            return tmp_out
+        out = so.sum3(x.data, self.Conv2.run(ll).data, self.Conv3.run(tmp_out).data, want_stats)
+        return _in_relu(out) if want_stats else Feat(out)
+
+
+class P2CResnetBlock(nn.Module):
+    """photo2cartoon.py:417-434 (no bias): x + IN(conv(relu(IN(conv(x))))), the fp32 result kept (its plane means are read)."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.conv_block = _seq(_1=P2CConv(dim, dim, 3, 1, 1, PAD_REFLECT), _5=P2CConv(dim, dim, 3, 1, 1, PAD_REFLECT))
+
+    def run(self, x):
+        y = self.conv_block['1'].run(x, norm_act=ACT_RELU)
+        y = self.conv_block['5'].run(y, norm_act=ACT_NONE)
+        return ops.materialize(y, residual=x, emit_xs=False)
+
+
+class P2CLIN(nn.Module):
+    """photo2cartoon.py:506-525; the reference's initial values."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.rho = nn.Parameter(torch.zeros(1, c, 1, 1))
+        self.gamma = nn.Parameter(torch.ones(1, c, 1, 1))
+        self.beta = nn.Parameter(torch.zeros(1, c, 1, 1))
+
+
+class P2CAdaLIN(nn.Module):
+    """photo2cartoon.py:488-503."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.rho = nn.Parameter(torch.full((1, c, 1, 1), 0.9))
+
+
+class P2CSoftAdaLIN(nn.Module):
+    """photo2cartoon.py:459-485.  The (N, C)-vector MLPs are stock torch (plumbing); the statistics and the normalisation are
+    aps_lin_coeffs + aps_affine_apply."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.norm = P2CAdaLIN(c)
+        self.w_gamma = nn.Parameter(torch.zeros(1, c))
+        self.w_beta = nn.Parameter(torch.zeros(1, c))
+        self.c_gamma = nn.Sequential(nn.Linear(c, c), nn.ReLU(True), nn.Linear(c, c))
+        self.c_beta = nn.Sequential(nn.Linear(c, c), nn.ReLU(True), nn.Linear(c, c))
+        self.s_gamma = nn.Linear(c, c)
+        self.s_beta = nn.Linear(c, c)
+
+    def coeffs(self, raw, content, style):
+        from . import style_ops as so
+        gamma = (1. - self.w_gamma) * self.s_gamma(style) + self.w_gamma * self.c_gamma(content)
+        beta = (1. - self.w_beta) * self.s_beta(style) + self.w_beta * self.c_beta(content)
+        return so.lin_coeffs(raw, self.norm.rho, gamma, beta)
+
+
+class P2CSoftAdaLINBlock(nn.Module):
+    """photo2cartoon.py:436-457."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.conv1 = P2CConv(dim, dim, 3, 1, 1, PAD_REFLECT)
+        self.norm1 = P2CSoftAdaLIN(dim)
+        self.conv2 = P2CConv(dim, dim, 3, 1, 1, PAD_REFLECT)
+        self.norm2 = P2CSoftAdaLIN(dim)
+
+    def run(self, x, content, style):
+        from . import style_ops as so
+        raw = self.conv1.run(x).data
+        a, b = self.norm1.coeffs(raw, content, style)
+        raw = self.conv2.run(Feat(so.affine_apply(raw, a, b, so.ACT_RELU))).data
+        a, b = self.norm2.coeffs(raw, content, style)
+        return Feat(so.affine_apply(raw, a, b, so.ACT_NONE, residual=x.data))
+
+
+class Photo2CartoonGenerator(nn.Module):
+    """``ResnetGenerator(ngf, img_size, light=True)`` of Module2/models/photo2cartoon.py:166-291 (the U-GAT-IT-style
+    generator of the third-party Photo2Cartoon project), forward only: the static cartoon of the streaming-inference model
+    (geomcgt_ifw_test_model.py:228-229, 286-291).  ``state_dict()`` has the reference's key names, order and shapes, so
+    ``load_state_dict(torch.load('cartoon.pt')['genA2B'], strict=True)`` works -- including the keys that do not influence
+    the image (``gap_fc.bias``, ``gmp_fc.bias``, every ``ConvBlock4``).
+
+    Convolutions: libapamd.so through ops.conv2d, producer InstanceNorm + ReLU fused into the consumer's loads.  LIN /
+    adaLIN, joins, pools, up-sampling adds and plane means: libapstyle.so (style_ops).  The class-activation stage needs
+    no kernel of its own: ``conv1x1(cat[x w_gap, x w_gmp])`` is a 1x1 convolution of x with the host-folded weight
+    ``W[:, :C] w_gap + W[:, C:] w_gmp``; ``cam_logit`` and ``heatmap`` have no reader and are not computed."""
+
+    def __init__(self, ngf=32, img_size=256, light=True):
+        super().__init__()
+        if not light:
+            raise NotImplementedError('Photo2CartoonGenerator: light=False (a fully connected layer over the whole feature map) '
+                                      'is not built; the published checkpoint is light=True')
+        if ngf < 4 or ngf % 4:
+            raise ValueError('Photo2CartoonGenerator: ngf = %d must be a positive multiple of 4' % ngf)
+        self.ngf, self.img_size = ngf, img_size
+        dim = ngf * 4
+        self.ConvBlock1 = _seq(_1=P2CConv(3, ngf, 7, 1, 3, PAD_REFLECT))
+        self.HourGlass1 = P2CHourGlass(ngf, ngf)
+        self.HourGlass2 = P2CHourGlass(ngf, ngf)
+        self.DownBlock1 = _seq(_1=P2CConv(ngf, ngf * 2, 3, 2, 1, PAD_REFLECT))
+        self.DownBlock2 = _seq(_1=P2CConv(ngf * 2, dim, 3, 2, 1, PAD_REFLECT))
+        for i in '1234':
+            setattr(self, 'EncodeBlock' + i, P2CResnetBlock(dim))
+        self.gap_fc = nn.Linear(dim, 1)
+        self.gmp_fc = nn.Linear(dim, 1)
+        self.conv1x1 = P2CConv(dim * 2, dim, 1, bias=True)
+        self._cam_spec = ConvSpec([dim], dim, 1)
+        self._cam_spec.precision = ops.PRECISION_FP32
+        self._cam_packed = None          # (key, packed image of the folded weight)
+        self.FC = nn.Sequential(nn.Linear(dim, dim), nn.ReLU(True), nn.Linear(dim, dim), nn.ReLU(True))
+        for i in '1234':
+            setattr(self, 'DecodeBlock' + i, P2CSoftAdaLINBlock(dim))
+        self.UpBlock1 = _seq(_2=P2CConv(dim, ngf * 2, 3, 1, 1, PAD_REFLECT), _3=P2CLIN(ngf * 2))
+        self.UpBlock2 = _seq(_2=P2CConv(ngf * 2, ngf, 3, 1, 1, PAD_REFLECT), _3=P2CLIN(ngf))
+        self.HourGlass3 = P2CHourGlass(ngf, ngf)
+        self.HourGlass4 = P2CHourGlass(ngf, ngf, False)
+        self.ConvBlock2 = _seq(_1=P2CConv(3, 3, 7, 1, 3, PAD_REFLECT))
+
+    def _cam(self, x):
+        """relu(conv1x1(cat[x w_gap, x w_gmp]) + bias) as ONE 1x1 convolution of x (photo2cartoon.py:257-269)."""
+        w, wg, wm = self.conv1x1.weight, self.gap_fc.weight, self.gmp_fc.weight
+        key = tuple(ops.weight_key(t) for t in (w, wg, wm))
+        if self._cam_packed is None or self._cam_packed[0] != key:
+            c = wg.shape[1]
+            folded = (w.detach()[:, :c] * wg.detach().view(1, c, 1, 1) + w.detach()[:, c:] * wm.detach().view(1, c, 1, 1)).contiguous()
+            self._cam_packed = (key, ops.pack_weights(self._cam_spec, folded))
+        return ops.conv2d(self._cam_spec, [x], self._cam_packed[1], self.conv1x1.bias.detach(), act=ACT_RELU)
+
+    def _up_lin(self, blk, x, want_stats):
+        """nn.Upsample(2) -> reflect 3x3 convolution -> LIN -> ReLU (photo2cartoon.py:221-231)."""
+        from . import style_ops as so
+        raw = blk['2'].run(Feat(so.up2_add(x))).data
+        lin = blk['3']
+        a, b = so.lin_coeffs(raw, lin.rho, lin.gamma, lin.beta)
+        return so.affine_apply(raw, a, b, so.ACT_RELU, want_stats=want_stats)
+
+    def forward(self, x):
+        """G(x) -> (N, 3, H, W), the tanh image (element [0] of the reference's forward)."""
+        from . import style_ops as so
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 16 or x.shape[3] % 16 or min(x.shape[2:]) < 32:
+            raise ValueError('Photo2CartoonGenerator: input of shape %s; served: (N, 3, H, W) with H and W multiples of 16, at '
+                             'least 32 (two stride-2 layers, four pooling levels, reflection pads)' % (tuple(x.shape),))
+        with torch.no_grad():
+            f = self.ConvBlock1['1'].run(Feat(x.contiguous()), norm_act=ACT_RELU)
+            # relu(IN(raw)) is read three ways by the first hourglass (normalised again, pooled, added): written once,
+            # as an affine map of the raw output, together with ITS statistics
+            rstd = f.rstd
+            f = _in_relu(so.affine_apply(f.data, rstd, -f.mean * rstd, so.ACT_RELU, want_stats=True))
+            f = self.HourGlass1.run(f, True)
+            f = self.HourGlass2.run(f, False)
+            f = self.DownBlock1['1'].run(f, norm_act=ACT_RELU)
+            f = self.DownBlock2['1'].run(f, norm_act=ACT_RELU)
+            f = ops.materialize(f, emit_xs=False)
+            content = []
+            for i in '1234':
+                f = getattr(self, 'EncodeBlock' + i).run(f)
+                content.append(so.plane_mean(f.data))
+            f = self._cam(f)
+            style = self.FC(so.plane_mean(f.data))
+            for i, cf in zip('1234', reversed(content)):
+                f = getattr(self, 'DecodeBlock' + i).run(f, cf, style)
+            y = self._up_lin(self.UpBlock1, f.data, False)
+            f = _in_relu(self._up_lin(self.UpBlock2, y, True))
+            f = self.HourGlass3.run(f, True)
+            f = self.HourGlass4.run(f)
+            return self.ConvBlock2['1'].run(f, act=ACT_TANH).data
+
+
 class NLayerDiscriminator(nn.Module):
     """70x70 PatchGAN, networks.py:2602-2647 (n_layers=3, instance norm)."""
 
