@@ -2,7 +2,7 @@
 //
 // Every tile family is instantiated in its own translation unit (conv_bf3_inst_*.hip), as the fp32 kernels are
 // (conv_registry.h): the instantiations are independent and the build runs them in parallel, and one family can be
-// rebuilt without the host file.  conv_host.hip sees only the entries below.
+// rebuilt without the host files.  The planner (conv_plan.hip) builds the table; the host files see only the entries below.
 #pragma once
 #include <vector>
 
@@ -35,7 +35,7 @@ static Bf3Kernel bk2(const char* name) {
                      &C::wfloats, &C::lds_bytes, name, reinterpret_cast<const void*>(&conv_bf16x3<C1>), &C1::lds_bytes};
 }
 
-// one function per translation unit; the order of the calls in conv_host.hip is the registry's order
+// one function per translation unit; the order of the calls in conv_plan.hip is the registry's order
 void bf3_register_k3_tall(std::vector<Bf3Kernel>&);      // 3x3 s1: 64 couts x 16 rows (the generator's dominant kernel)
 void bf3_register_k3_short(std::vector<Bf3Kernel>&);     // 3x3 s1, small batches: 64 couts x 4 rows
 void bf3_register_s2k3(std::vector<Bf3Kernel>&);         // 3x3 s2: 64 couts x 4 rows

@@ -2,7 +2,7 @@
 //   ap_conv_final_dgrad_bf16   data gradient of the generator's last 7x7 layer (dgrad_k7.h: dgrad_k7_final_kernel)
 //   ap_conv_head_dgrad_bf16    data gradient of the PatchGAN's output layer (dgrad_k7.h: dgrad_head_kernel)
 //   ap_conv_d0_fwd_bf16        the PatchGAN's first layer as an output stream (conv_d0.h)
-// Their weight gradients are in wgrad_host.hip.
+// Their weight gradients are in wgrad_edge_host.hip (the last layer's vector-ALU one, ap_conv_final_wgrad, in wgrad_launch.hip).
 #include "common.h"
 #include "wgrad_k7.h"
 #include "dgrad_k7.h"

@@ -844,7 +844,7 @@ def _wgrad_buffers(nfloats, what, out, out_shape, device):
 
 
 # Everything the backward route decisions read besides the forms of the tensors (form_of): the module switches and the environment
-# variables the C side reads per call for its plan queries (wgrad_host.hip: make_wgrad_plan, the xs predicates; conv_host.hip:
+# variables the C side reads per call for its plan queries (wgrad_plan.hip: make_wgrad_plan, the xs predicates; conv_plan.hip:
 # make_plan behind ap_conv2d_wants_presplit; ap_instnorm_bwd_split_ok) and s2d_eligible reads here.  Tests and A/B runs flip them
 # inside one process: every cached decision is keyed by backward_switches().  A new switch of a backward route is listed HERE.
 _WGRAD_XS_ENV = ('APAMD_NO_XS_DIRECT', 'APAMD_NO_XS_WGRAD', 'APAMD_NO_BF16X3', 'APAMD_NO_S2D_WGRAD', 'APAMD_ROWS_WGRAD',

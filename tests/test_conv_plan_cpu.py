@@ -1,6 +1,6 @@
 """CPU (-m "not gpu"): the convolution planner's answers, pinned.  tests/golden/conv_plans.json holds what every plan query of the
 C ABI answered for a sweep of descriptors at commit e450293 (the parent of the change that split make_plan and conv2d_fwd_impl in
-csrc/conv_host.hip into named steps); this test replays the sweep and compares every field for equality.  The plan reads shapes
+what was then csrc/conv_host.hip into named steps; the planner is csrc/conv_plan.hip now); this test replays the sweep and compares every field for equality.  The plan reads shapes
 only, never memory, and without a GPU the planner assumes 256 compute units -- the MI355X's count -- so the table is the same on
 both kinds of machine.
 

@@ -1,6 +1,6 @@
 """CPU (-m "not gpu"): the reach of tests/test_wgrad_edges_gpu.py.  Without a device the planner assumes 256 compute units, the
 MI355X's count, so ap_conv2d_wgrad_route answers here what it answers there: every route a GPU case states must be the planner's
-answer, and the stated routes together must name every entry of the four kernel tables of csrc/wgrad_host.hip (kWgradKernels,
+answer, and the stated routes together must name every entry of the four kernel tables of csrc/wgrad_launch.hip (kWgradKernels,
 kWgradBf3Kernels, kWgradNarrowKernels, kWgradXsKernels) and every operand form, as ap_conv2d_wgrad_route_names lists them.  A
 kernel added later without a case fails here.
 

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): every weight-gradient family at the edges of its planner (csrc/wgrad_host.hip: make_wgrad_plan), against fp64.
+"""GPU (-m gpu): every weight-gradient family at the edges of its planner (csrc/wgrad_plan.hip: make_wgrad_plan), against fp64.
 
 tests/test_wgrad_plan_cpu.py pins what the planner ANSWERS on both sides of every branch; this module RUNS the kernels there.
 Each case of CASES is one small layer and states the route it is meant to exercise, in the words of ap_conv2d_wgrad_route
