@@ -12,6 +12,7 @@
 
 #include "../../../include/animateportrait_data.h"
 #include "apd_common.h"
+#include "pil_resample.h"
 
 namespace apd {
 
@@ -30,7 +31,9 @@ using apd::fail;
 using apd::g_err;
 
 constexpr int TW = 64, TH = 16, THREADS = 256;
-constexpr int PRECISION_BITS = 32 - 8 - 2;       // Pillow: Resample.c
+using pil::PRECISION_BITS;                       // Pillow: Resample.c (pil_resample.h, shared with the face library)
+using pil::clampi;
+using pil::clip8;
 constexpr int MAX_LDS_BYTES = 48 * 1024;
 
 // Pillow's ksize for one axis; 0 when the axis keeps its size (the pass is skipped)
@@ -57,10 +60,6 @@ struct Args {
     float* out;
     int Hs, Ws, C, OC, gray, load_w, load_h, crop, kh, kv, rows_cap;
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ int clip8(int acc) { return clampi(acc >> PRECISION_BITS, 0, 255); }
 
 // one 8-bit sample of channel ch at column col of an interleaved row
 __device__ __forceinline__ int fetch(const uint8_t* row, int col, int C, int ch, int gray) {

@@ -44,9 +44,16 @@ def tensor2im(t):
     return ((np.transpose(a, (1, 2, 0)) + 1) / 2.0 * 255.0).astype(np.uint8)
 
 
-def load_photo(path, size):
+def load_photo(path, size, align='none', mtcnn_weights=None):
+    """``align='mtcnn'``: the photo is first aligned in process as the reference's align_mtcnn does (animateportrait_amd.mtcnn)"""
     from PIL import Image
     im = Image.open(path).convert('RGB')
+    if align == 'mtcnn':
+        from . import mtcnn
+        aligned = mtcnn.Detector(mtcnn_weights or mtcnn.DEFAULT_WEIGHTS).align_photo(np.asarray(im))
+        if aligned is None:
+            raise SystemExit('--align mtcnn: no face found in %s' % path)
+        im = Image.fromarray(aligned)
     if im.size != (size, size):
         im = im.resize((size, size), Image.BICUBIC)
     a = np.asarray(im, dtype=np.float32) / 255.0
@@ -92,6 +99,11 @@ def landmarks_from_audio(a, device):
 def make_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--photo', required=True)
+    ap.add_argument('--align', choices=('none', 'mtcnn'), default='none',
+                    help='mtcnn: detect the face and cut the aligned 512 x 512 picture from --photo on the device before anything '
+                         'else reads it (align_mtcnn, main_end2end_module2.py:12-45); none: --photo is already aligned')
+    ap.add_argument('--mtcnn_weights', default=None, help='with --align mtcnn: pnet.npy / rnet.npy / onet.npy directory or .npz '
+                                                          '(default: MTCNN/weights)')
     ap.add_argument('--landmarks', default=None, help='directory in the Alm_txt layout')
     ap.add_argument('--landmarks_npy', default=None)
     ap.add_argument('--landmark_scale', type=float, default=1.0)
@@ -305,7 +317,7 @@ def main(argv=None, prepare_model=None):
     else:
         arr = np.load(a.landmarks_npy).astype(np.float32) * a.landmark_scale
         lm0, seq = arr[0], arr[1:]
-    photo = load_photo(a.photo, a.size)
+    photo = load_photo(a.photo, a.size, a.align, a.mtcnn_weights)
     matte = load_matte(a.matte, a.size) if a.matte else None
     if matte is None and model.aux.get('modnet') is None:
         raise SystemExit('no matting network is attached (aux["modnet"]): pass --matte PNG')
