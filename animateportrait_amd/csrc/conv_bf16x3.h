@@ -26,15 +26,18 @@
 //     from stage g's barrier on; the pieces are awaited at stage g+1's): the split 3x3 stride-1 tiles spread the
 //     pieces over it, one per D MFMAs (bf3_dma_sched), the other families issue them all in the last tap of stage g;
 //   * epilogue identical to the fp32 kernel (bias, activation, InstanceNorm partial statistics).
+// Where the steps are: the raw LDS-DMA issue and the fragment type -- lds_dma.h; piece geometry per tile, the scalar addresses
+// of a stage, the issue of a piece / a stage and the spread schedule (bf3_dma_sched) -- conv_bf3_dma.h; the stage's barrier with
+// the experiment build's cycle stamps (AP_STAMP), the tile walk, fragment fetch, `stage`, the chunk loops, the epilogue and the
+// tile hand-over -- the kernel below.
 #pragma once
 #include <type_traits>
 #include <utility>
 
 #include "conv_igemm.h"
+#include "lds_dma.h"      // bf16x8, split_bf16, the raw LDS-DMA issue (glds16_sv / glds16_si, dma_wait_all), static_for
 
 namespace apamd {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // K_ > 0: dense K x K taps.  K_ == 0: NTAP_ (1, 2 or 4) taps at run-time offsets inside a 2 x 2 window (the
 // sub-pixel phases of a stride-2 transposed convolution); the count is a template parameter so that the tap
@@ -96,70 +99,30 @@ struct Bf3Cfg {
     }
 };
 
-__device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)v;
-    lo = (__bf16)(v - (float)hi);
-}
-
 struct Bf3Tile {
     int n, cot, ty, tx;
 };
 
-// Where the NPIECE LDS-DMA pieces of chunk c+2 are issued.  Their target, the buffer of stage c, is free from stage c's barrier
-// on, and they only have to have landed at the barrier of stage c+1: the window is the last tap of stage c (NM MFMA slots) plus
-// the taps of stage c+1 that leave two whole taps in front of that barrier.  D = the largest distance (in MFMA slots) at which
-// one piece per D slots still fits the window; piece j < N0 goes behind slot (j + 1) * D - 1 of the last tap of stage c, piece
-// N0 + t * PPT + k behind slot (k + 1) * D - 1 of tap t <= LAST_ISSUE_TAP of stage c+1.
-// D == 0: no window (fewer than four taps per stage, or not enabled) -- every piece in the last tap of stage c.
-struct Bf3DmaSched {
-    int D, LAST_ISSUE_TAP, PPT, N0;
-};
-constexpr Bf3DmaSched bf3_dma_sched(bool enabled, int npiece, int nm, int nreal) {
-    const int taps = nreal - 3;                                    // taps of stage c+1 that may carry pieces
-    if (enabled && taps >= 1)
-        for (int d = nm; d >= 1; --d) {
-            const int ppt = nm / d;
-            if ((taps + 1) * ppt >= npiece) {
-                const int n0 = ppt < npiece ? ppt : npiece;
-                return {d, (npiece - n0 + ppt - 1) / ppt - 1, ppt, n0};
-            }
-        }
-    return {0, -1, 0, npiece};
-}
+}  // namespace apamd
 
-// LDS-DMA issued behind the compiler's back.  With the builtin, the compiler books every in-flight
-// global_load_lds as a "flat access that may touch LDS" and degrades each later s_waitcnt on an LDS read to
-// lgkmcnt(0) for as long as the DMA is pending -- i.e. through the whole MFMA stage this kernel overlaps it with.
-// Raw issue keeps the fragment-read waits exact; the price is that completion must be awaited explicitly
-// (dma_wait_all) before the barrier that publishes the stage.  lds_addr: wave-uniform LDS byte address of
-// lane 0's 16 bytes (lane i lands at +16 i).
-// Source address = scalar base + per-lane unsigned 32-bit byte offset.
-__device__ __forceinline__ void glds16_sv(const void* sbase, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr)
-                 : "memory", "m0");
-}
-// The same with the LDS address as scalar base + compile-time offset: one s_add into M0 per piece.  (Passing each piece's
-// LDS address as a value kept 19 scalars alive per stage; with ~100 SGPRs in use the compiler spilled them into VGPR lanes
-// and read them back with v_readlane in front of every piece: profiles/r05_dominant_cycle_account.md.)
-template <int IMM>
-__device__ __forceinline__ void glds16_si(const void* sbase, unsigned voff, unsigned lds_base) {
-    asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_base), "n"(IMM)
-                 : "memory", "m0", "scc");
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// the kernel's units, each with what it reads and writes (they use Bf3Tile and take the tile configuration as C)
+#include "conv_bf3_dma.h"
 
-template <class F, int... J>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, J...>) {
-    (f(std::integral_constant<int, J>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
+namespace apamd {
 
 // seg[s].data of the bf16x3 kernel points to an XS tensor (see split_prepass_kernel); seg[s].C = channels.
 // Launch with min(#tiles, #CUs) workgroups of 256 threads; needs nchunks >= 2.
 // (head-only arithmetic halves the LDS image: two workgroups per CU, i.e. two waves per SIMD and <= 256 registers each)
+// The DMA unit (conv_bf3_dma.h) is a struct of references into this frame -- the shape of the `[&]` closures it was, which is
+// what kept every instantiation's machine code (tools/kernel_isa_diff.py is the gate for any further move).  Two things decide
+// whether a lambda can leave this body unchanged.  A callee is optimised on its own before it is inlined, so what stands in
+// the body itself (pgeo, woff, slots, the pending-refill set-up, the hand-over) differs once it is inside a callee, without the
+// kernel's knowledge of tid and wave.  And a lambda sees `smem`, `wbuf` and `xbuf` as the LDS symbol itself (const locals with
+// constant initialisers are not captured), which a unit handed them by reference does not.
+// Measured, and therefore still lambdas: the epilogue (by-reference struct or function: every instantiation; naming the LDS
+// symbol itself: the experiment build identical, the product build of the run-time-tap and row families not, e.g.
+// Bf3Cfg<1,0,1,2,4,2,4,0,1,1,0> 25306 -> 25114 instructions), the fetch forms (both ways, e.g. Bf3Cfg<1,0,1,2,4,2,4,0,2,1,0>),
+// the cycle stamps (three stamped instantiations: other register numbers).  `stage` calls all of these and stays with them.
 template <class C>
 __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKParams p) {
     constexpr int S = C::S, K = C::K, TMAX = C::TMAX, MT = C::MT, NT = C::NT, WCO = C::WCO;
@@ -246,13 +209,6 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
     }
     if (tile >= tile_end) return;
 
-    auto seg_of = [&](int chunk) {
-        int s = 0;
-        if (p.nseg > 1 && chunk >= p.seg[1].chunk_begin) s = 1;
-        if (p.nseg > 2 && chunk >= p.seg[2].chunk_begin) s = 2;
-        return s;
-    };
-
     // ---- DMA geometry: piece k of this thread covers slot it = tid + k*256 of a part = (k-group, tile pixel);
     // source = that pixel of the image (reflected) or the all-zero slot (zero padding, tile padding)
     int pgeo[NIT];      // (k-group << 15) | (ly << 8) | lx of the piece, or -1 beyond the tile
@@ -269,104 +225,18 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
         if constexpr (S == 2) lx = lx < IWE ? 2 * lx : 2 * (lx - IWE) + 1;
         pgeo[k] = it < 2 * PLANE ? ((kg << 15) | (ly << 8) | lx) : -1;
     }
-    auto locate = [&](int logical, Bf3Tile& t, int (&goff)[NIT]) __attribute__((always_inline)) {
-        t.cot = logical % p.co_tiles;
-        int t_ = logical / p.co_tiles;
-        t.tx = t_ % p.tiles_x;
-        t_ /= p.tiles_x;
-        t.ty = t_ % p.tiles_y;
-        t.n = t_ / p.tiles_y;
-        int dy0 = p.dy0, dx0 = p.dx0;
-        if (p.nphase > 1) {                                    // fused sub-pixel phases: the phase sets the window origin
-            const int ph = t.cot / p.co_tiles_phase;
-            dy0 = p.ph_dy0[ph];
-            dx0 = p.ph_dx0[ph];
-        }
-        const int iy0 = t.ty * C::TH * S + dy0, ix0 = t.tx * 32 * S + dx0;
-#pragma unroll
-        for (int k = 0; k < NIT; ++k) {
-            int gy = iy0 + ((pgeo[k] >> 8) & 127), gx = ix0 + (pgeo[k] & 255);
-            bool ok = pgeo[k] >= 0;
-            if (p.pad_mode == 1) {
-                gy = reflect_clamp(gy, H);
-                gx = reflect_clamp(gx, W);
-            } else {
-                ok = ok && gy >= 0 && gy < H && gx >= 0 && gx < W;
-            }
-            // byte offset from the chunk's first channel-group plane; out-of-image pixels read that plane's zero slot
-            goff[k] = (ok ? ((pgeo[k] >> 15) & 1) * (HW + 1) + gy * W + gx : HW) * 16;
-        }
-    };
-    // ---- LDS-DMA of one stage = NPIECE wave-wide 1 KiB pieces per wave: 2 * NIT activation pieces (head, tail) and
-    // the wave's share of the weight image.  DmaCtx holds the scalar part of the addresses.
-    // A piece is {s_mov m0; global_load_lds v_off, s[base]}: the per-lane 32-bit byte offsets are constants of the
-    // tile (goff) or of the kernel (woff), everything that changes per stage is scalar -- so a piece costs no
-    // vector ALU work and slots between two MFMAs of the stage's last tap.
-    struct DmaCtx {
-        const unsigned char* xh;   // the chunk's first head plane of image n (scalar)
-        const unsigned char* xl;   // ... and tail plane
-        const unsigned char* wsrc; // the (cout tile, chunk) weight block (scalar)
-        unsigned xdst, wdst;       // LDS byte addresses of the stage's activation / weight images (this wave's lane 0)
-        unsigned wmask;            // S2D3: taps of the chunk's input phase -- the weight pieces of the others are not staged (the
-                                   // stage never reads them).  With the fragment reads of absent taps gone the kernel is bound by
-                                   // the LDS-DMA (1.15 MB per CU against 27 k MFMA cycles, profiles/r04p_pmc_*): 19 % fewer bytes
-    };
-    constexpr int NWP = (W_SLOTS / 64 + 3) / 4, NPIECE = PARTS * NIT + NWP;
+    using Dma = Bf3Dma<C>;                                         // locate, setup, piece, issue: conv_bf3_dma.h
+    constexpr int NWP = Dma::NWP, NPIECE = Dma::NPIECE;
     unsigned woff[NWP];            // byte offset of this lane's slot in weight piece j
 #pragma unroll
     for (int j = 0; j < NWP; ++j) woff[j] = ((j * 4 + wave) * 64 + lane) * 16;
-    // The scalar part of a stage's addresses, computed ONCE per stage and pinned in SGPRs (the empty asm): left to itself the
-    // compiler re-derived the 64-bit plane address in front of every piece (ten scalar multiplies / adds per piece).
-    // The padding chunk of an odd count (chunk_ >= nreal: its weights are all zero) stages the last real chunk's activations
-    // again -- finite data, so the products are exact zeros -- instead of skipping its pieces under a per-piece branch.
-    auto dma_setup = [&](int n, int cot, int chunk_, int buf) __attribute__((always_inline)) {
-        const int chunk = chunk_ < nreal ? chunk_ : nreal - 1;
-        const int s = seg_of(chunk);
-        const int cg0 = (chunk - p.seg[s].chunk_begin) * 2;          // first channel group of the chunk
-        const int CG = p.seg[s].C >> 3;
-        const unsigned char* xs = reinterpret_cast<const unsigned char*>(p.seg[s].data);
-        const unsigned char* xh = xs + ((long long)(n * 2 + 0) * CG + cg0) * (HW + 1) * 16;
-        const unsigned char* xl = xs + ((long long)(n * 2 + 1) * CG + cg0) * (HW + 1) * 16;
-        unsigned xdst = lds0 + (buf * STAGE + W_SLOTS + wave * 64) * 16;
-        const unsigned char* wsrc = reinterpret_cast<const unsigned char*>(p.wp + ((long long)cot * nchunks + chunk_) * p.wfloats);
-        unsigned wdst = lds0 + (buf * STAGE + wave * 64) * 16;
-        unsigned wmask = 0xFu;
-        if constexpr (C::S2D3) wmask = p.s2d_mask[chunk_ / p.s2d_div < 3 ? chunk_ / p.s2d_div : 3];
-        asm volatile("" : "+s"(xh), "+s"(xl), "+s"(wsrc), "+s"(xdst), "+s"(wdst));
-        return DmaCtx{xh, xl, wsrc, xdst, wdst, wmask};
-    };
-    // piece j (a compile-time index): {s_add m0; global_load_lds v_off, s[base]} -- nothing else
-    // (alt / use_alt: the tile's tail stage takes the NEXT tile's offsets; selected here, per piece, on registers -- a
-    // selected copy of the array was kept in scratch memory)
-    auto dma_piece = [&](const DmaCtx& d, const int (&goff)[NIT], const int (&alt)[NIT], bool use_alt, auto jt) __attribute__((always_inline)) {
-        constexpr int j = decltype(jt)::value;
-        if constexpr (j < PARTS * NIT) {
-            constexpr int part = j / NIT, k = j % NIT;
-            constexpr bool whole = k * 256 + 3 * 64 < XP;           // every wave's slice of the piece lies inside the part
-            if (whole || k * 256 + wave * 64 < XP)                  // (wave-uniform)
-                glds16_si<(part * XP + k * 256) * 16>(part ? d.xl : d.xh, (unsigned)(use_alt ? alt[k] : goff[k]), d.xdst);
-        } else {
-            constexpr int jj = j - PARTS * NIT;
-            constexpr bool whole = jj * 4 + 3 < W_SLOTS / 64;
-            bool want = whole || jj * 4 + wave < W_SLOTS / 64;
-            // weight image [part][tap][k-group][CO_TILE] in 64-slot pieces: piece -> tap (wave-uniform)
-            if constexpr (C::S2D3) want = want && ((d.wmask >> (((jj * 4 + wave) % (T * 2 * CO_TILE / 64)) / (2 * CO_TILE / 64))) & 1u);
-            if (want) glds16_si<jj * 4096>(d.wsrc, woff[jj], d.wdst);
-        }
-    };
-    auto issue = [&](const Bf3Tile& t, const int (&goff)[NIT], int chunk_, int buf) __attribute__((always_inline)) {
-        const DmaCtx d = dma_setup(t.n, t.cot, chunk_, buf);
-        static_for<NPIECE>([&](auto jt) __attribute__((always_inline)) { dma_piece(d, goff, goff, false, jt); });
-    };
-    // ---- the issue schedule (bf3_dma_sched) and the state a stage hands to the next one: the pieces N0 .. NPIECE-1 of the chunk
-    // it staged are issued during the next stage's taps 0 .. LAST_ISSUE_TAP, from the SAME pinned scalars and per-lane offsets
-    // (no select, no address arithmetic between those pieces and the MFMAs), under the same scalar flag.
-    constexpr int NM_STAGE = (PARTS == 2 ? 3 : 1) * MT * NT;       // MFMA slots of a tap
-    constexpr Bf3DmaSched SCHED = bf3_dma_sched(C::DMA_SPREAD, NPIECE, NM_STAGE, TMAX);
-    constexpr int DMA_D = SCHED.D, LAST_ISSUE_TAP = SCHED.LAST_ISSUE_TAP, DMA_PPT = SCHED.PPT, DMA_N0 = SCHED.N0;
-    DmaCtx pend;
+    // the issue schedule (bf3_dma_sched) and the state a stage hands to the next one: conv_bf3_dma.h
+    constexpr int NM_STAGE = Dma::NM_STAGE;                        // MFMA slots of a tap
+    constexpr int DMA_D = Dma::DMA_D, LAST_ISSUE_TAP = Dma::LAST_ISSUE_TAP, DMA_PPT = Dma::DMA_PPT, DMA_N0 = Dma::DMA_N0;
+    Bf3DmaCtx pend;
     int pig[NIT];
     int pdma;
+    const Dma dma{p, wave, H, W, HW, nchunks, nreal, lds0, pgeo, woff, pend, pig, pdma};
 
     // fragment addresses (16-byte slots)
     const int a_slot = half * CO_TILE + wco * MT * 32 + l32;                       // + ((part*T + t)*2) * CO_TILE + m*32
@@ -454,10 +324,10 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
 
     Bf3Tile cur, nxt;
     int cgoff[NIT], ngoff[NIT];
-    locate(tile, cur, cgoff);
+    dma.locate(tile, cur, cgoff);
     AP_STAMP(7, 0);                                                // kernel entry (tile geometry done)
-    issue(cur, cgoff, 0, 0);
-    issue(cur, cgoff, 1, 1);
+    dma.issue(cur, cgoff, 0, 0);
+    dma.issue(cur, cgoff, 1, 1);
     dma_wait_all();
     __syncthreads();
     AP_STAMP(8, 0);                                                // first two stages landed
@@ -465,7 +335,7 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
     // from constants: a zero shared with a vector register's initial value turns the whole carried chain into vector registers,
     // which the raw assembly of a piece cannot take.)
     if constexpr (DMA_D > 0) {
-        pend = dma_setup(cur.n, cur.cot, 1, 1);
+        pend = dma.setup(cur.n, cur.cot, 1, 1);
         asm volatile("s_mov_b32 %0, 0" : "=s"(pdma));
 #pragma unroll
         for (int k = 0; k < NIT; ++k) pig[k] = cgoff[k];
@@ -479,7 +349,7 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
     unsigned tmask = tapmask_of(cur);
     for (;;) {
         const bool has_next = tile + tile_step < tile_end;
-        locate(has_next ? tile + tile_step : tile, nxt, ngoff);
+        dma.locate(has_next ? tile + tile_step : tile, nxt, ngoff);
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -581,7 +451,7 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
                             static_for<LAST_ISSUE_TAP + 1>([&](auto tt) __attribute__((always_inline)) {
                                 constexpr int j = DMA_N0 + decltype(tt)::value * DMA_PPT + i / DMA_D;
                                 if constexpr (j < NPIECE) {
-                                    if (ti == decltype(tt)::value && pdma) dma_piece(pend, pig, pig, false, std::integral_constant<int, j>{});
+                                    if (ti == decltype(tt)::value && pdma) dma.piece(pend, pig, pig, false, std::integral_constant<int, j>{});
                                 }
                             });
                         }
@@ -638,7 +508,7 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
                     // instead of 32, ~1000 cycles per stage, profiles/r05_dominant_cycle_account.md.)
                     const bool more = c + 1 < nchunks;
                     const bool tail = c + 2 >= nchunks;
-                    const DmaCtx d = dma_setup(tail ? nxt.n : cur.n, tail ? nxt.cot : cur.cot, tail ? 0 : c + 2, P);
+                    const Bf3DmaCtx d = dma.setup(tail ? nxt.n : cur.n, tail ? nxt.cot : cur.cot, tail ? 0 : c + 2, P);
                     // (the offset selects sit HERE, in front of the barrier: vector selects on SGPR-pair masks between LDS-DMA
                     // pieces and MFMAs are what makes a kernel disturb a co-resident one, profiles/r04_cohazard.md)
                     int ig[NIT];
@@ -655,20 +525,20 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
                     // (the MFMAs stay in straight-line code: with them inside the two arms of a branch the accumulators became phi
                     // nodes and the allocator moved all 128 between AGPRs and VGPRs every stage)
                     // (as scalar integers: left as `bool`s the compiler parks the condition in a VGPR and tests it from there)
-                    const int dma = __builtin_amdgcn_readfirstlane((more && !AP_ABLATE(p, 1)) ? 1 : 0);
+                    const int dma_on = __builtin_amdgcn_readfirstlane((more && !AP_ABLATE(p, 1)) ? 1 : 0);
                     static_for<NM>([&](auto it) __attribute__((always_inline)) {
                         constexpr int i = decltype(it)::value;
                         if (real_tap) mfma_one(i);
                         if constexpr (DMA_D > 0) {
                             // the first N0 pieces, one behind every D-th MFMA; the others ride on the next stage's taps
                             if constexpr (i % DMA_D == DMA_D - 1 && i / DMA_D < DMA_N0) {
-                                if (dma) dma_piece(d, ig, ig, false, std::integral_constant<int, i / DMA_D>{});
+                                if (dma_on) dma.piece(d, ig, ig, false, std::integral_constant<int, i / DMA_D>{});
                             }
                         } else {
                             static_for<PPS>([&](auto ppt) __attribute__((always_inline)) {
                                 constexpr int j = i * PPS + decltype(ppt)::value;
                                 if constexpr (j < NPIECE) {
-                                    if (dma) dma_piece(d, ig, ig, false, std::integral_constant<int, j>{});
+                                    if (dma_on) dma.piece(d, ig, ig, false, std::integral_constant<int, j>{});
                                 }
                             });
                         }
@@ -686,7 +556,7 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
                     });
                     if constexpr (DMA_D > 0) {                     // the rest of this refill: the next stage's first taps
                         pend = d;
-                        pdma = dma;
+                        pdma = dma_on;
 #pragma unroll
                         for (int k = 0; k < NIT; ++k) pig[k] = ig[k];
                     }
@@ -1133,14 +1003,14 @@ __global__ __launch_bounds__(256, C::WG_PER_CU) void conv_bf16x3(const ConvKPara
         if constexpr (DMA_D > 0) {
             // the next tile's chunk 1 is "the refill of stage -1": its first N0 pieces here, the others on the taps of the
             // next tile's stage 0, like every other refill (stage_sync(0) awaits them; stage 1 reads them)
-            pend = dma_setup(nxt.n, nxt.cot, 1, pl);
+            pend = dma.setup(nxt.n, nxt.cot, 1, pl);
             pdma = __builtin_amdgcn_readfirstlane(AP_ABLATE(p, 1) ? 0 : 1);
 #pragma unroll
             for (int k = 0; k < NIT; ++k) pig[k] = ngoff[k];
             static_for<DMA_N0>([&](auto jt) __attribute__((always_inline)) {
-                if (pdma) dma_piece(pend, pig, pig, false, jt);
+                if (pdma) dma.piece(pend, pig, pig, false, jt);
             });
-        } else if (!AP_ABLATE(p, 1)) issue(nxt, ngoff, 1, pl);
+        } else if (!AP_ABLATE(p, 1)) dma.issue(nxt, ngoff, 1, pl);
         AP_STAMP(6, 0);                                            // the next tile's chunk 1 is on its way
 #ifdef APAMD_ABLATION
         ++stamp_tile;

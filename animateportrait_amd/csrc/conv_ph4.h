@@ -13,7 +13,8 @@
 #pragma once
 #include <utility>
 
-#include "conv_bf16x3.h"
+#include "conv_igemm.h"
+#include "lds_dma.h"
 
 namespace apamd {
 

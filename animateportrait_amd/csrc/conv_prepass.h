@@ -2,7 +2,8 @@
 // two convolutions, and the row and space-to-depth split copies.  Included by conv_prepass_host.hip only (the convolution kernels
 // themselves are instantiated one tile family per translation unit, conv_bf3_inst_*.hip; the weight packer is conv_pack.h).
 #pragma once
-#include "conv_bf16x3.h"
+#include "conv_igemm.h"
+#include "lds_dma.h"
 
 namespace apamd {
 

@@ -23,7 +23,8 @@
 //     ring row, ky = 6 closes it (bias, activation, store).  Only ONE row of T is live per buffer -- never the tile's.
 // LDS: 2 x 17,408 (staged rows) + 2 x 14,112 (T rows) + 2,048 (ring) = 65,088 bytes: two workgroups per CU.
 #pragma once
-#include "conv_bf16x3.h"
+#include "conv_igemm.h"
+#include "lds_dma.h"
 
 namespace apamd {
 

@@ -20,7 +20,7 @@
 #pragma once
 #include <type_traits>
 
-#include "conv_bf16x3.h"
+#include "lds_dma.h"
 #include "wgrad_igemm.h"
 
 namespace apamd {

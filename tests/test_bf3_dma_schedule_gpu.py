@@ -1,5 +1,5 @@
 """GPU: the split-bf16 3x3 kernel spreads the LDS-DMA pieces of a stage's refill over the taps of the following stage
-(csrc/conv_bf16x3.h ``bf3_dma_sched``; profiles/r07_dma_spread.md).  The change reorders loads only, so a layer's output,
+(csrc/conv_bf3_dma.h ``bf3_dma_sched``; profiles/r07_dma_spread.md).  The change reorders loads only, so a layer's output,
 mean and rstd are bit-identical however the persistent workgroups walk the tile list, and agree with an fp64 convolution
 on the host within the bar of test_gpu_parity.py::test_conv_bf16x3_persistent_walk (InstanceNorm-ed output within 2e-3).
 

@@ -1,6 +1,6 @@
 """CPU: checks on the ISA of the built library (no GPU needed: llvm-objdump of the gfx950 code objects inside libapamd.so).
 
-The LDS-DMA primitive of the matrix kernels (csrc/conv_bf16x3.h ``glds16_sv``, wgrad_bf16x3.h, conv_ph4.h) writes M0 inside
+The LDS-DMA primitive of the matrix kernels (csrc/lds_dma.h ``glds16_sv``: conv_bf16x3.h, wgrad_bf16x3.h, conv_ph4.h) writes M0 inside
 inline assembly and lists it as clobbered; hipcc warns that a clobber of a reserved register "may lead to undefined behaviour"
 because its register allocator does not model M0.  That is only a hazard if the COMPILER ever keeps a value of its own in M0
 across such a statement or emits an instruction that reads M0 implicitly.  This test makes the assumption a checked one: in
@@ -83,7 +83,7 @@ def test_m0_is_touched_only_by_the_lds_dma_assembly(tmp_path):
     """Per kernel: M0 is written either ONLY by the raw assembly (scalar-base form ``global_load_lds_dwordx4 vN, s[a:b]``, its
     ``s_mov_b32 m0`` directly in front, nothing but s_nop between) or ONLY by the compiler for its own builtin LDS-DMA (vector
     address form) -- never both in one kernel, where a compiler-held M0 value could straddle an assembly statement."""
-    # the two forms the assembly uses: a copy of a scalar, or scalar base + literal offset (conv_bf16x3.h glds16_sv / glds16_si)
+    # the two forms the assembly uses: a copy of a scalar, or scalar base + literal offset (lds_dma.h glds16_sv / glds16_si)
     M0_WRITE = re.compile(r'(s_mov_b32 m0, s\d+|s_add_u32 m0, s\d+, (0x[0-9a-f]+|\d+))$')
     implicit = re.compile(r'^\s*(s_movrel|v_movrel|s_sendmsg|ds_gws|ds_param_load|ds_direct_load|v_interp|s_ttrace)')
     n_raw = n_builtin = 0
