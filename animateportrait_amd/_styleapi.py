@@ -25,6 +25,10 @@ SIGNATURES = {
     'aps_affine_apply': (ctypes.c_int, [_ptr] * 3 + [_i32, _ptr] + [_i32] * 4 + [_ptr] * 4),
     'aps_plane_combine_ok': (_i32, [_i32] + [_ptr] * 4 + [_i32] * 7 + [_ptr] * 3),
     'aps_plane_combine': (ctypes.c_int, [_i32] + [_ptr] * 4 + [_i32] * 7 + [_ptr] * 4),
+    # cartoon training: luminance in front of the identity loss (added without an ABI change)
+    'aps_luma_ok': (_i32, [_ptr] * 2 + [_i32] * 3),
+    'aps_luma_fwd': (ctypes.c_int, [_ptr] + [_i32] * 3 + [_ptr] * 2),
+    'aps_luma_bwd': (ctypes.c_int, [_ptr] + [_i32] * 3 + [_ptr] * 2),
 }
 
 _lib = None

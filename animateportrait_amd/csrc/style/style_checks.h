@@ -106,4 +106,24 @@ inline int plan_plane_combine(int mode, const void* s0, const void* s1, const vo
     return APS_OK;
 }
 
+// Luminance (forward: in = frame of 3 planes, out = 1 plane; backward: the other way round).  A launch is (blocks, N) workgroups
+// of 256 lanes that walk `items` items per sample: float4 items when every plane of both tensors starts on a 16-byte boundary
+// (H W % 4 == 0 and aligned bases), else single floats -- with H W % 4 != 0 the plane starts are misaligned against each other,
+// so there is no common vector body to peel a tail from.
+struct LumaPlan {
+    int vec, blocks;
+    long items;
+};
+
+inline int plan_luma(const char* what, const void* in, const void* out, int N, int H, int W, LumaPlan* pl) {
+    if (!in || !out) return snprintf(err_buf(), 256, "%s: null pointer", what), APS_ERR_INVALID;
+    const int rc = check_shape(what, N, 3, H, W);
+    if (rc != APS_OK) return rc;
+    const long hw = (long)H * W;
+    pl->vec = (hw % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0) ? 4 : 1;
+    pl->items = hw / pl->vec;
+    pl->blocks = (int)((pl->items + 255) / 256 < 1024 ? (pl->items + 255) / 256 : 1024);
+    return APS_OK;
+}
+
 }  // namespace aps

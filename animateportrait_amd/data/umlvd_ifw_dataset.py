@@ -119,9 +119,10 @@ def transform_mask(mask, dx, dy):
     return torch.nn.functional.grid_sample(mask.unsqueeze(0), grid, align_corners=False)[0]
 
 
-def _siblings(path, kind):
-    """the reference's path rules: a photo under /Photo/ or a drawing under /Drawing/ -> the files that go with it"""
-    a, b = ('/Photo/', 'A') if '/Photo/' in path else ('/Drawing/', 'B')
+def _siblings(path, kind, b_folder='/Drawing/', static_folder='/fakeB_static/'):
+    """the reference's path rules: a photo under /Photo/ or a drawing under /Drawing/ (the cartoon dataset: /Cartoon/) -> the
+    files that go with it"""
+    a, b = ('/Photo/', 'A') if '/Photo/' in path else (b_folder, 'B')
     if kind == 'lm':
         return path.replace(a, '/%slm/MTCNN/' % b)
     if kind == 'txt':
@@ -129,7 +130,7 @@ def _siblings(path, kind):
     if kind == 'win':
         return path.replace(a, '/%slm_txt/MTCNN/' % b)[:-4] + '_win.txt'
     if kind == 'static':
-        return path.replace('/Photo/', '/fakeB_static/')
+        return path.replace('/Photo/', static_folder)
     return path.replace(a, '/%smask/%s/' % (b, kind))
 
 
@@ -142,6 +143,12 @@ def _list_images(folder, limit):
 
 class UMLVDIFWDataset:
     """Iterable of batches (already batched: ``opt.batch_size`` samples per item), tensors on ``cuda:<gpu_ids[0]>``."""
+    # what umlvd_ifw_cartoon_dataset.py changes: the folder of the B images, the folder of the static pictures, and whether the
+    # B side has video clips (scanner_frag_*: the B1 / B2 items, the get_params3 draws, the select_target12 branch)
+    B_FOLDER, STATIC_FOLDER, HAS_CLIPS = '/Drawing/', '/fakeB_static/', True
+
+    def sib(self, path, kind):
+        return _siblings(path, kind, self.B_FOLDER, self.STATIC_FOLDER)
 
     @staticmethod
     def modify_commandline_options(parser, is_train):
@@ -176,12 +183,13 @@ class UMLVDIFWDataset:
         if not self.A_paths or not self.B_paths:
             raise RuntimeError('umlvd_ifw: no images: neither the lists %s / %s nor %s/%sA|B hold any' % (list_a, list_b, opt.dataroot, opt.phase))
         clip_root = '/'.join(self.B_paths[0].split('/')[:-2])
-        self.B12_paths = [sorted(glob.glob(clip_root + '/scanner_frag_%d_MTCNN/*.png' % c)) for c in range(CLIPS)]
+        self.B12_paths = [sorted(glob.glob(clip_root + '/scanner_frag_%d_MTCNN/*.png' % c)) for c in range(CLIPS)] if self.HAS_CLIPS else []
         self.A_size, self.B_size = len(self.A_paths), len(self.B_paths)
         self.B12_size = sum(len(c) for c in self.B12_paths)
         print('A size:', self.A_size)
         print('B size:', self.B_size)
-        print('B12 size:', self.B12_size)
+        if self.HAS_CLIPS:
+            print('B12 size:', self.B12_size)
         btoa = opt.direction == 'BtoA'
         self.input_nc = opt.output_nc if btoa else opt.input_nc
         self.output_nc = opt.input_nc if btoa else opt.output_nc
@@ -214,26 +222,27 @@ class UMLVDIFWDataset:
         index_b = index % self.B_size if opt.serial_batches else random.randint(0, self.B_size - 1)
         p['B_path'] = B_path = self.B_paths[index_b]
         size_a, size_b = self._size(A_path), self._size(B_path)
-        lm_a, lm_b = read_landmarks(_siblings(A_path, 'txt')), read_landmarks(_siblings(B_path, 'txt'))
+        lm_a, lm_b = read_landmarks(self.sib(A_path, 'txt')), read_landmarks(self.sib(B_path, 'txt'))
         p['pA'] = crop_params_face(opt, size_a)
         p['pB'] = crop_params_face(opt, size_b)
         p['A_lm_68'], p['winA'] = trans_lm(lm_a, p['pA'], opt, size_a)
         p['B_lm_68'], p['winBr'] = trans_lm(lm_b, p['pB'], opt, size_b)
         p['image_paths'] = os.path.basename(A_path)[:-4] + '->' + os.path.basename(B_path)[:-4] + '.png'
 
-        clip = random.randint(0, len(self.B12_paths) - 1)
-        frame = random.randint(0, len(self.B12_paths[clip]) - 2)
-        p['B1_path'], p['B2_path'] = B1_path, B2_path = self.B12_paths[clip][frame], self.B12_paths[clip][frame + 1]
-        size_b1 = self._size(B1_path)
-        lm_b1, lm_b2 = read_landmarks(_siblings(B1_path, 'txt')), read_landmarks(_siblings(B2_path, 'txt'))
-        win1, win2 = read_window(_siblings(B1_path, 'win')), read_window(_siblings(B2_path, 'win'))
-        p['pB1'] = crop_params_windows(opt, size_b1, win1, win2)
-        p['B1_lm_68'], p['winBr1'] = trans_lm(lm_b1, p['pB1'], opt, size_b1, win1)
-        p['B2_lm_68'], p['winBr2'] = trans_lm(lm_b2, p['pB1'], opt, size_b1, win2)
+        if self.HAS_CLIPS:
+            clip = random.randint(0, len(self.B12_paths) - 1)
+            frame = random.randint(0, len(self.B12_paths[clip]) - 2)
+            p['B1_path'], p['B2_path'] = B1_path, B2_path = self.B12_paths[clip][frame], self.B12_paths[clip][frame + 1]
+            size_b1 = self._size(B1_path)
+            lm_b1, lm_b2 = read_landmarks(self.sib(B1_path, 'txt')), read_landmarks(self.sib(B2_path, 'txt'))
+            win1, win2 = read_window(self.sib(B1_path, 'win')), read_window(self.sib(B2_path, 'win'))
+            p['pB1'] = crop_params_windows(opt, size_b1, win1, win2)
+            p['B1_lm_68'], p['winBr1'] = trans_lm(lm_b1, p['pB1'], opt, size_b1, win1)
+            p['B2_lm_68'], p['winBr2'] = trans_lm(lm_b2, p['pB1'], opt, size_b1, win2)
 
         p['r'] = r = random.random()
         p['dxdy'] = None
-        if r <= opt.select_target12_thre:
+        if self.HAS_CLIPS and r <= opt.select_target12_thre:
             p['branch'] = 0
             p['tB_lm_68'], p['tB2_lm_68'] = p['B1_lm_68'].clone(), p['B2_lm_68'].clone()
             p['winB'], p['winB2'] = p['winBr1'].clone(), p['winBr2'].clone()
@@ -269,30 +278,33 @@ class UMLVDIFWDataset:
         for i, p in enumerate(plans):
             def par(q):
                 return (q[0], q[1], int(q[2] and not opt.no_flip))
-            pa, pb, pb1 = par(p['pA']), par(p['pB']), par(p['pB1'])
+            pa, pb = par(p['pA']), par(p['pB'])
             br = p['branch']
-            A, B, B1, B2 = p['A_path'], p['B_path'], p['B1_path'], p['B2_path']
+            A, B = p['A_path'], p['B_path']
+            if self.HAS_CLIPS:
+                pb1, B1, B2 = par(p['pB1']), p['B1_path'], p['B2_path']
             jobs.append((A, True, pa, gray_in, 'image', [('A', i)]))
             jobs.append((B, True, pb, gray_out, 'image', [('B', i)]))
-            jobs.append((_siblings(A, 'lm'), False, pa, True, 'image', [('A_lm', i), ('tA_lm', i)] + ([('tB_lm', i)] if br == 2 else [])))
-            jobs.append((_siblings(B, 'lm'), False, pb, True, 'image', [('B_lm', i)] + ([('tB_lm', i)] if br == 1 else [])))
+            jobs.append((self.sib(A, 'lm'), False, pa, True, 'image', [('A_lm', i), ('tA_lm', i)] + ([('tB_lm', i)] if br == 2 else [])))
+            jobs.append((self.sib(B, 'lm'), False, pb, True, 'image', [('B_lm', i)] + ([('tB_lm', i)] if br == 1 else [])))
             for suf, folder in parts:
                 both = [('B_mask' + suf, i), ('B2_mask' + suf, i)]
-                jobs.append((_siblings(A, folder), False, pa, True, 'mask', [('A_mask' + suf, i)] + (both if br == 2 else [])))
-                jobs.append((_siblings(B, folder), False, pb, True, 'mask', [('Br_mask' + suf, i)] + (both if br == 1 else [])))
-            jobs.append((B1, True, pb1, gray_out, 'image', [('B1', i)]))
-            jobs.append((B2, True, pb1, gray_out, 'image', [('B2', i)]))
+                jobs.append((self.sib(A, folder), False, pa, True, 'mask', [('A_mask' + suf, i)] + (both if br == 2 else [])))
+                jobs.append((self.sib(B, folder), False, pb, True, 'mask', [('Br_mask' + suf, i)] + (both if br == 1 else [])))
+            if self.HAS_CLIPS:
+                jobs.append((B1, True, pb1, gray_out, 'image', [('B1', i)]))
+                jobs.append((B2, True, pb1, gray_out, 'image', [('B2', i)]))
             if br == 0:           # the clip's own landmark maps and masks are the targets (the reference prepares them always)
-                jobs.append((_siblings(B1, 'lm'), False, pb1, True, 'image', [('tB_lm', i)]))
-                jobs.append((_siblings(B2, 'lm'), False, pb1, True, 'image', [('tB2_lm', i)]))
+                jobs.append((self.sib(B1, 'lm'), False, pb1, True, 'image', [('tB_lm', i)]))
+                jobs.append((self.sib(B2, 'lm'), False, pb1, True, 'image', [('tB2_lm', i)]))
                 for suf, folder in parts:
-                    jobs.append((_siblings(B1, folder), False, pb1, True, 'mask', [('B_mask' + suf, i)]))
-                    jobs.append((_siblings(B2, folder), False, pb1, True, 'mask', [('B2_mask' + suf, i)]))
+                    jobs.append((self.sib(B1, folder), False, pb1, True, 'mask', [('B_mask' + suf, i)]))
+                    jobs.append((self.sib(B2, folder), False, pb1, True, 'mask', [('B2_mask' + suf, i)]))
             if opt.coh_use_more:
                 jobs.append((p['B3_path'], True, pb, gray_out, 'image', [('B3', i)]))
                 jobs.append((p['B4_path'], True, pb, gray_out, 'image', [('B4', i)]))
             if getattr(opt, 'isTrain', True) and (getattr(opt, 'warp_loss', 2) == 2 or getattr(opt, 'identity_loss', 2) == 2):
-                jobs.append((_siblings(A, 'static'), True, pa, gray_out, 'image', [('fakeB_static', i)]))
+                jobs.append((self.sib(A, 'static'), True, pa, gray_out, 'image', [('fakeB_static', i)]))
         return jobs
 
     def _decode_one(self, key):
@@ -375,14 +387,16 @@ class UMLVDIFWDataset:
 
         def stack(key):
             return torch.stack([p[key] for p in plans])
-        lms = torch.stack([stack(k) for k in ('A_lm_68', 'B_lm_68', 'tB_lm_68', 'tB2_lm_68', 'B1_lm_68', 'B2_lm_68')]).to(dev)
-        for j, k in enumerate(('A_lm_68', 'B_lm_68', 'tB_lm_68', 'tB2_lm_68', 'B1_lm_68', 'B2_lm_68')):
+        clips = self.HAS_CLIPS
+        lm_keys = ('A_lm_68', 'B_lm_68', 'tB_lm_68', 'tB2_lm_68') + (('B1_lm_68', 'B2_lm_68') if clips else ())
+        lms = torch.stack([stack(k) for k in lm_keys]).to(dev)
+        for j, k in enumerate(lm_keys):
             item[k] = lms[j]
         item['tA_lm_68'] = item['A_lm_68'].clone()
-        for k in ('winA', 'winBr', 'winBr1', 'winBr2', 'winB', 'winB2'):
+        for k in ('winA', 'winBr') + (('winBr1', 'winBr2') if clips else ()) + ('winB', 'winB2'):
             item[k] = stack(k)
-        for key, k in (('A_paths', 'A_path'), ('B_paths', 'B_path'), ('B1_path', 'B1_path'), ('B2_path', 'B2_path'),
-                       ('image_paths', 'image_paths')):
+        for key, k in (('A_paths', 'A_path'), ('B_paths', 'B_path')) + ((('B1_path', 'B1_path'), ('B2_path', 'B2_path')) if clips else ()) \
+                + (('image_paths', 'image_paths'),):
             item[key] = [p[k] for p in plans]
 
         drawn = [i for i, p in enumerate(plans) if p['branch'] != 0]     # second target drawn from landmarks: cv2.circle, radius 3 / 5

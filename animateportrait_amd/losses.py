@@ -141,6 +141,35 @@ def masked(a, mask, mask_type):
     return _Composite.apply(a, mask.detach(), None, mode, mask_type >= 2)
 
 
+class _Luminance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        from . import _styleapi as S
+        x = x.contiguous()
+        _require_device(x, 'luminance input')
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError('luminance: a (B, 3, H, W) frame is expected, got %s' % (tuple(x.shape),))
+        n, _, h, w = x.shape
+        y = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
+        S.check(S.lib().aps_luma_fwd(_ptr(x), n, h, w, _ptr(y), _stream()), 'luma_fwd')
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _styleapi as S
+        g = g.contiguous()
+        n, _, h, w = g.shape
+        gx = torch.empty((n, 3, h, w), dtype=torch.float32, device=g.device)
+        S.check(S.lib().aps_luma_bwd(_ptr(g), n, h, w, _ptr(gx), _stream()), 'luma_bwd')
+        return gx
+
+
+def luminance(x):
+    """0.299 R + 0.587 G + 0.114 B of a (B, 3, H, W) frame as a (B, 1, H, W) plane, one HIP launch each way
+    (geomgm_ifw_cartoon_fore_model.py:745-748, the ATen chain's bits; csrc/style/style_luma.hip)."""
+    return _Luminance.apply(x)
+
+
 def axpy_(dst, src, alpha=1.0):
     """dst += alpha * src on flat fp32 buffers (gradient accumulation into an optimiser's flat buffer)."""
     if dst.numel() != src.numel():

@@ -37,10 +37,16 @@ LIP_SEGMENTS = [(i, i + 1) for i in range(48, 59)] + [(59, 48)] + [(i, i + 1) fo
 
 
 class GeomGMIFWForeModel(BaseModel):
-    @staticmethod
-    def modify_commandline_options(parser, is_train=True):
+    # what geomgm_ifw_cartoon_fore_model.py changes in the option surface (its :165, :195, :197, :200, :203): the defaults of
+    # --dataset_mode / --coherent / --coh_use_more, and whether the video-clip options exist (--select_target12_thre, --rx/ry/rs)
+    DATASET_MODE = 'umlvd_ifw'
+    COHERENT, COH_USE_MORE = 1, 2
+    VIDEO_TARGET_OPTIONS = True
+
+    @classmethod
+    def modify_commandline_options(cls, parser, is_train=True):
         parser.set_defaults(no_dropout=True)
-        parser.set_defaults(dataset_mode='umlvd_ifw')
+        parser.set_defaults(dataset_mode=cls.DATASET_MODE)
         parser.set_defaults(netG='resnet_9blocks_rcatland3')
         parser.add_argument('--netg_resb_div', type=int, default=3)
         parser.add_argument('--netg_resb_disp', type=int, default=1)
@@ -61,16 +67,18 @@ class GeomGMIFWForeModel(BaseModel):
             parser.add_argument('--warp_loss', type=int, default=2)
             parser.add_argument('--lambda_warp', type=float, default=5.0)
             parser.add_argument('--lambda_warp_inter', type=float, default=5.0)
-            parser.add_argument('--coherent', type=int, default=1)
+            parser.add_argument('--coherent', type=int, default=cls.COHERENT)
             parser.add_argument('--lambda_G_A_coh', type=float, default=0.5)
-            parser.add_argument('--coh_use_more', type=int, default=2)
+            parser.add_argument('--coh_use_more', type=int, default=cls.COH_USE_MORE)
             parser.add_argument('--check_fakeb2_in_backwardD', type=int, default=1)
-            parser.add_argument('--select_target12_thre', type=float, default=0.2)
+            if cls.VIDEO_TARGET_OPTIONS:
+                parser.add_argument('--select_target12_thre', type=float, default=0.2)
             parser.add_argument('--select_noniden_thre', type=float, default=0.9)
             parser.add_argument('--more_weight_for_lip', type=int, default=0)
-            parser.add_argument('--rx', type=float, default=0.15)
-            parser.add_argument('--ry', type=float, default=0.2)
-            parser.add_argument('--rs', type=float, default=0.7)
+            if cls.VIDEO_TARGET_OPTIONS:
+                parser.add_argument('--rx', type=float, default=0.15)
+                parser.add_argument('--ry', type=float, default=0.2)
+                parser.add_argument('--rs', type=float, default=0.7)
         return parser
 
     def __init__(self, opt):
@@ -300,6 +308,17 @@ class GeomGMIFWForeModel(BaseModel):
         self.loss_D_A_coh = loss.detach()
 
     # ------------------------------------------------------------------ G loss
+    def identity_pair(self, fl):
+        """:741-752: the two frames the identity loss compares -- the generated drawing and, by --identity_loss, the photo's
+        luminance (1) or the static drawing (2)."""
+        # networks.FaceLoss reads a 1-channel drawing three times itself; other callables get the x3 repeat of :745-750
+        rep = (lambda x: x) if isinstance(fl, networks.FaceLoss) else \
+            (lambda x: x.repeat(1, 3, 1, 1) if x.shape[1] == 1 else x)         # noqa: E731
+        if self.opt.identity_loss == 1:
+            gray = 0.299 * self.real_A[:, 0:1] + 0.587 * self.real_A[:, 1:2] + 0.114 * self.real_A[:, 2:3]
+            return rep(self.fake_B), rep(gray)
+        return rep(self.fake_B), rep(self.fakeB_static)
+
     def backward_G(self):
         """:677-780."""
         o, crit = self.opt, self.criterionGAN
@@ -341,6 +360,8 @@ class GeomGMIFWForeModel(BaseModel):
             self._notice('landmarks', 'no landmark regressor: geometry loss (lambda_geom) is skipped')
         if o.lambda_geom_lipline > 0:                                             # :715-719
             m1, m2 = self.getlipline(self.target_B_lm_68), self.getlipline(self.target_B2_lm_68)
+            if self.fake_B.shape[1] != 1:       # torch.mean((fake_B + 1) * mask) broadcasts the mask over a colour frame's channels
+                m1, m2 = m1.expand_as(self.fake_B).contiguous(), m2.expand_as(self.fake_B2).contiguous()
             self.loss_geom_B_lipline = (losses.weighted_mean(self.fake_B, m1, 1.0)
                                         + losses.weighted_mean(self.fake_B2, m2, 1.0)) * o.lambda_geom_lipline
             loss = loss + self.loss_geom_B_lipline
@@ -353,15 +374,8 @@ class GeomGMIFWForeModel(BaseModel):
         loss = loss + self.loss_warp_inter1
         if self.aux['faceloss'] is not None and o.identity_loss in (1, 2):        # :741-752
             fl = self.aux['faceloss']
-            # networks.FaceLoss reads a 1-channel drawing three times itself; other callables get the x3 repeat of :745-750
-            rep = (lambda x: x) if isinstance(fl, networks.FaceLoss) else \
-                (lambda x: x.repeat(1, 3, 1, 1) if x.shape[1] == 1 else x)         # noqa: E731
-            if o.identity_loss == 1:
-                gray = 0.299 * self.real_A[:, 0:1] + 0.587 * self.real_A[:, 1:2] + 0.114 * self.real_A[:, 2:3]
-                other = rep(gray)
-            else:
-                other = rep(self.fakeB_static)
-            self.loss_iden_B = torch.mean(fl(rep(self.fake_B), other, bbox1=self.winB, bbox2=self.winA)) * o.lambda_face
+            mine, other = self.identity_pair(fl)
+            self.loss_iden_B = torch.mean(fl(mine, other, bbox1=self.winB, bbox2=self.winA)) * o.lambda_face
             loss = loss + self.loss_iden_B
         elif o.identity_loss:
             self._notice('faceloss', 'no face-recognition network: identity loss (lambda_face) is skipped')

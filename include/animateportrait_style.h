@@ -77,6 +77,18 @@ int aps_plane_combine(int32_t mode, const float* s0, const float* s1, const floa
                       int32_t H, int32_t W, int32_t Hs, int32_t Ws, int32_t flags, float* y, float* mean_out, float* rstd_out,
                       void* stream);
 
+/* Luminance of a 3-channel cartoon frame, the input of the identity loss of cartoon TRAINING
+ * (geomgm_ifw_cartoon_fore_model.py:745-748):  y = 0.299 x[:, 0] + 0.587 x[:, 1] + 0.114 x[:, 2], each product rounded and the
+ * sum taken left to right in fp32, as the ATen chain does (same bits).
+ *   x (N, 3, H, W) -> y (N, 1, H, W);   aps_luma_bwd: g (N, 1, H, W) -> gx (N, 3, H, W), gx[:, c] = k_c g
+ * One pass over HBM each.  128-bit loads and stores when H W % 4 == 0 and both pointers are 16-byte aligned (every plane then
+ * starts on a 16-byte boundary), element by element otherwise.
+ * Added without changing an existing call, so APS_ABI_VERSION stays 1; a binding finds a library that predates them by the
+ * missing symbol. */
+int32_t aps_luma_ok(const float* in, const float* out, int32_t N, int32_t H, int32_t W);
+int aps_luma_fwd(const float* x, int32_t N, int32_t H, int32_t W, float* y, void* stream);
+int aps_luma_bwd(const float* g, int32_t N, int32_t H, int32_t W, float* gx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
