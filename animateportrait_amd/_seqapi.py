@@ -1,0 +1,62 @@
+"""ctypes binding of libapseq.so (C ABI declared in include/animateportrait_seq.h): the batched LSTM forward of Module1's
+landmark networks.  Separate from _capi.py / libapamd.so, the boundary a model integrator binds.
+Loaded on first use; as there, a missing library or a failed call raises -- there is no silent fallback."""
+import ctypes
+import os
+import threading
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get('APSEQ_LIB') or os.path.join(_HERE, 'libapseq.so')
+
+ABI_VERSION = 1      # APQ_ABI_VERSION of include/animateportrait_seq.h this binding was written against
+LSTM_H = 256
+MAX_B, MAX_T, MAX_I = 1048576, 65536, 512
+ALIGN_WIDE, ALIGN_ELEM = 16, 4
+OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_LAUNCH = 0, -1, -2, -3
+
+_i32, _ptr = ctypes.c_int32, ctypes.c_void_p
+# name -> (restype, argtypes); every symbol include/animateportrait_seq.h declares
+SIGNATURES = {
+    'apq_abi_version': (_i32, []),
+    'apq_last_error': (ctypes.c_char_p, []),
+    'apq_lstm_layer_fwd_ok': (_i32, [_ptr] * 6 + [_i32] * 5),
+    'apq_lstm_layer_fwd': (ctypes.c_int, [_ptr] * 6 + [_i32] * 5 + [_ptr]),
+}
+
+_lib = None
+_lock = threading.Lock()
+
+
+def lib():
+    """Load libapseq.so once; raise loudly when it has not been built."""
+    global _lib
+    if _lib is None:
+        with _lock:
+            if _lib is None:
+                if not os.path.exists(LIB_PATH):
+                    raise RuntimeError('animateportrait_amd: %s not found. Build it with `make -C animateportrait_amd/csrc`. '
+                                       'The batched LSTM has no path without it.' % LIB_PATH)
+                l = ctypes.CDLL(LIB_PATH)
+                for name, (res, args) in SIGNATURES.items():
+                    if not hasattr(l, name):
+                        raise RuntimeError('animateportrait_amd: %s is stale: it lacks %s. Rebuild it '
+                                           '(make -C animateportrait_amd/csrc)' % (LIB_PATH, name))
+                    fn = getattr(l, name)
+                    fn.restype = res
+                    fn.argtypes = args
+                if l.apq_abi_version() != ABI_VERSION:
+                    raise RuntimeError('animateportrait_amd: %s speaks seq ABI %d, this binding %d: rebuild the library '
+                                       '(make -C animateportrait_amd/csrc)' % (LIB_PATH, l.apq_abi_version(), ABI_VERSION))
+                _lib = l
+    return _lib
+
+
+def last_error():
+    msg = lib().apq_last_error()
+    return msg.decode() if msg else '?'
+
+
+def check(rc, what=''):
+    if rc < 0:
+        raise RuntimeError('libapseq %s failed (%d): %s' % (what, rc, last_error()))
+    return rc

@@ -78,6 +78,8 @@ def landmarks_from_audio(a, device):
     std_z = np.loadtxt(a.std_face).reshape(68, 3)[:, 2] if a.std_face else None
     face_id, scale, shift = module1.adjust_and_norm_input_face(shape, std_z)
     net_g, net_c = module1.load_module1(a.load_a2l_G_name, a.load_a2l_C_name, device)
+    if a.module1_lstm is not None:
+        module1.set_lstm_backend(a.module1_lstm)
     emb = np.loadtxt(a.speaker_emb).reshape(-1).astype(np.float32)
     converter = None
     if not a.no_autovc:
@@ -124,6 +126,9 @@ def make_parser():
     ap.add_argument('--std_face', default=None, help='STD_FACE_LANDMARKS.txt (its depth column replaces the detected one)')
     ap.add_argument('--load_a2l_G_name', default='Module1/checkpoints/ckpt_speaker_branch.pth')
     ap.add_argument('--load_a2l_C_name', default='Module1/checkpoints/ckpt_content_branch.pth')
+    ap.add_argument('--module1_lstm', choices=('library', 'hip'), default=None,
+                    help='who runs the LSTMs of the two Module1 networks: library = nn.LSTM, hip = the batched kernel of '
+                         'libapseq.so, one launch per layer (default: library, or what APAMD_MODULE1_LSTM names)')
     ap.add_argument('--max_frames', type=int, default=None)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--size', type=int, default=256)

@@ -11,8 +11,8 @@ Mirrors of the reference's two networks, attribute for attribute, so that its ch
   MLP.  The reference also constructs a ``Decoder`` it never runs; it is built here too because its tensors are in the
   checkpoint.
 
-Both run ONCE per clip over all windows: stock PyTorch-ROCm, as the hot-path scope prescribes for Module1 (no hand
-kernels).  ``predict_landmarks_speaker_aware`` is ``Audio2landmark_model.test`` (train_audio2landmark.py:101-141,
+Both run ONCE per clip over all windows: stock PyTorch-ROCm by default; ``set_lstm_backend('hip')`` (or
+APAMD_MODULE1_LSTM=hip) moves their LSTMs to the batched kernel of libapseq.so.  ``predict_landmarks_speaker_aware`` is ``Audio2landmark_model.test`` (train_audio2landmark.py:101-141,
 235-245, 247-309, 594-617) followed by the clip-level post-processing of main_end2end_module2.py:262-272; the simpler
 ``predict_landmarks`` is the content branch alone (``__train_face_wo_pos__``).  NOT built: the AutoVC mel / speaker
 embedding front end (librosa / pysptk / pyworld / resemblyzer are not in this image, and neither are the checkpoints);
@@ -20,6 +20,7 @@ callers pass the (T, 18, 80) mel windows and the 256-d speaker embedding the ref
 """
 import copy
 import math
+import os
 
 import numpy as np
 import torch
@@ -29,6 +30,38 @@ import torch.nn.functional as F
 from .stream import smooth_landmarks
 
 FACE_ID_FEAT_SIZE = 204       # 68 x 3, model_audio2landmark.py:23
+
+# Who runs the two 3-layer LSTMs at inference on the device: 'library' = nn.LSTM (MIOpen), 'hip' = one apq_lstm_layer_fwd
+# launch per layer (lstm_hip.lstm_forward_batched, libapseq.so).  CPU tensors, training mode and autograd always take nn.LSTM.
+LSTM_BACKENDS = ('library', 'hip')
+
+
+def _checked_backend(name):
+    if name not in LSTM_BACKENDS:
+        raise ValueError('Module1 LSTM backend %r (known: %s)' % (name, ', '.join(LSTM_BACKENDS)))
+    return name
+
+
+_lstm_backend = _checked_backend(os.environ.get('APAMD_MODULE1_LSTM') or 'library')
+
+
+def set_lstm_backend(name):
+    """Select the LSTM backend of both landmark networks; returns the previous one."""
+    global _lstm_backend
+    prev, _lstm_backend = _lstm_backend, _checked_backend(name)
+    return prev
+
+
+def get_lstm_backend():
+    return _lstm_backend
+
+
+def _lstm_last(lstm, x):
+    """``lstm(x)[0][:, -1, :]``, the one thing both networks read from their LSTM"""
+    if _lstm_backend == 'hip':
+        from . import lstm_hip
+        return lstm_hip.lstm_forward_batched(lstm, x, last_only=True)
+    return lstm(x)[0][:, -1, :]
 
 
 def _mlp3(cin, h1, h2, cout, slope):
@@ -55,8 +88,7 @@ class Audio2LandmarkContent(nn.Module):
         x = au
         if self.use_prior_net:
             x = self.fc_prior(x.contiguous().view(-1, self.in_size)).view(-1, self.num_window_frames, self.lstm_size)
-        output, _ = self.bilstm(x)
-        output = output[:, -1, :]
+        output = _lstm_last(self.bilstm, x)
         if face_id.shape[0] == 1:
             face_id = face_id.repeat(output.shape[0], 1)
         return self.fc(torch.cat((output, face_id), dim=1)), face_id
@@ -209,7 +241,7 @@ class Audio2LandmarkPos(nn.Module):
         self.out = _mlp3(d_model + z_size, 512, 256, 204, 0.02)
 
     def forward(self, au, emb, face_id, fls=None, z=None):                       # :354-386 (add_z_spk=False)
-        audio_encode = self.audio_content_encoder(au)[0][:, -1, :]
+        audio_encode = _lstm_last(self.audio_content_encoder, au)
         if self.use_audio_projection:
             audio_encode = self.audio_projection(audio_encode)
         spk_encode = self.spk_emb_encoder(emb)
