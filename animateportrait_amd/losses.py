@@ -55,6 +55,8 @@ class _ReduceMean(torch.autograd.Function):
         a, b = ctx.saved_tensors
         op, c, weight = ctx.args
         ga = gb = None
+        if ctx.needs_input_grad[1] and op != RED_L1:        # also when a asks for one too: never a silent None
+            raise NotImplementedError('gradient w.r.t. the weight map of a weighted mean is not defined on the HIP path')
         if ctx.needs_input_grad[0] or (ctx.needs_input_grad[1] and op == RED_L1):
             ga = torch.empty_like(a)
             C.check(C.lib().ap_reduce_mean_bwd(op, _ptr(a), _ptr(b), c, a.numel(), weight, _ptr(gout.contiguous()),
@@ -63,8 +65,6 @@ class _ReduceMean(torch.autograd.Function):
                 gb = -ga
             if not ctx.needs_input_grad[0]:
                 ga = None
-        elif ctx.needs_input_grad[1]:
-            raise NotImplementedError('gradient w.r.t. the weight map of a weighted mean is not defined on the HIP path')
         return ga, gb, None, None, None
 
 
