@@ -1,5 +1,5 @@
 """ctypes binding of libapseq.so (C ABI declared in include/animateportrait_seq.h): the batched LSTM forward of Module1's
-landmark networks.  Separate from _capi.py / libapamd.so, the boundary a model integrator binds.
+landmark networks and the clip-level post-processing of their landmark sequence.  Separate from _capi.py / libapamd.so, the boundary a model integrator binds.
 Loaded on first use; as there, a missing library or a failed call raises -- there is no silent fallback."""
 import ctypes
 import os
@@ -14,13 +14,26 @@ MAX_B, MAX_T, MAX_I = 1048576, 65536, 512
 ALIGN_WIDE, ALIGN_ELEM = 16, 4
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_LAUNCH = 0, -1, -2, -3
 
-_i32, _ptr = ctypes.c_int32, ctypes.c_void_p
+LM_C, SG_MIN_W, SG_MAX_W, SEG_MAX_T, MAX_STAMPS = 204, 5, 31, 512, 4096
+SEG_CLOSE, SEG_LIP, SEG_NOSE = 1, 2, 4
+IMG_TRANSFORM, IMG_EYES = 1, 2
+
+_i32, _ptr, _f32, _f64 = ctypes.c_int32, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
 # name -> (restype, argtypes); every symbol include/animateportrait_seq.h declares
 SIGNATURES = {
     'apq_abi_version': (_i32, []),
     'apq_last_error': (ctypes.c_char_p, []),
     'apq_lstm_layer_fwd_ok': (_i32, [_ptr] * 6 + [_i32] * 5),
     'apq_lstm_layer_fwd': (ctypes.c_int, [_ptr] * 6 + [_i32] * 5 + [_ptr]),
+    # clip-level landmark post-processing (landmark_post.py); each launching call = its _ok twin + the stream
+    'apq_savgol_ok': (_i32, [_ptr] * 4 + [_i32] * 7),
+    'apq_savgol': (ctypes.c_int, [_ptr] * 4 + [_i32] * 7 + [_ptr]),
+    'apq_calib_baseline_ok': (_i32, [_ptr] * 2 + [_i32] * 2 + [_f32] * 2),
+    'apq_calib_baseline': (ctypes.c_int, [_ptr] * 2 + [_i32] * 2 + [_f32] * 2 + [_ptr]),
+    'apq_segment_assemble_ok': (_i32, [_ptr] * 4 + [_i32, _f64, _f32, _i32]),
+    'apq_segment_assemble': (ctypes.c_int, [_ptr] * 4 + [_i32, _f64, _f32, _i32, _ptr]),
+    'apq_image_landmarks_ok': (_i32, [_ptr] * 3 + [_i32] * 2 + [_f64] * 3 + [_i32]),
+    'apq_image_landmarks': (ctypes.c_int, [_ptr] * 3 + [_i32] * 2 + [_f64] * 3 + [_i32, _ptr]),
 }
 
 _lib = None

@@ -70,7 +70,8 @@ def load_matte(path, size):
 
 def landmarks_from_audio(a, device):
     """main_end2end_module2.py:205-272 in process (mel -> AutoVC conversion -> both Module1 networks -> post-processing), with
-    the clip's f0 track and speaker embedding as inputs: returns (photo landmarks (68, 2), clip (T, 68, 2)) px."""
+    the clip's f0 track and speaker embedding as inputs: returns (photo landmarks (68, 2), clip (T, 68, 2)) px.  With
+    --module1_post device the clip is a CUDA tensor that never was on the host."""
     from . import audio, module1
     shape = np.loadtxt(a.photo_landmarks).reshape(68, -1)
     if shape.shape[1] == 2:
@@ -80,6 +81,8 @@ def landmarks_from_audio(a, device):
     net_g, net_c = module1.load_module1(a.load_a2l_G_name, a.load_a2l_C_name, device)
     if a.module1_lstm is not None:
         module1.set_lstm_backend(a.module1_lstm)
+    if a.module1_post is not None:
+        module1.set_post_backend(a.module1_post)
     emb = np.loadtxt(a.speaker_emb).reshape(-1).astype(np.float32)
     converter = None
     if not a.no_autovc:
@@ -95,6 +98,8 @@ def landmarks_from_audio(a, device):
     windows = audio.clip_audio_features(a.wav, max_frames=a.max_frames, converter=converter)
     fl = module1.predict_landmarks_speaker_aware(net_g, net_c, windows, emb, face_id.reshape(-1))
     seq = module1.to_image_landmarks(fl, scale=scale, shift=shift)[:, :, :2]
+    if torch.is_tensor(seq):
+        return module1.photo_landmarks_in_pixels(face_id, scale, shift), seq.contiguous()
     return module1.photo_landmarks_in_pixels(face_id, scale, shift), seq.astype(np.float32)
 
 
@@ -129,6 +134,10 @@ def make_parser():
     ap.add_argument('--module1_lstm', choices=('library', 'hip'), default=None,
                     help='who runs the LSTMs of the two Module1 networks: library = nn.LSTM, hip = the batched kernel of '
                          'libapseq.so, one launch per layer (default: library, or what APAMD_MODULE1_LSTM names)')
+    ap.add_argument('--module1_post', choices=('host', 'device'), default=None,
+                    help='where Module1\'s landmark post-processing runs (Savitzky-Golay filters, baseline calibration, lip fixes, '
+                         'eye lids): host = numpy / scipy, device = libapseq.so, the landmark sequence then stays on the GPU; with '
+                         '--triangulate device it never leaves it (default: host, or what APAMD_MODULE1_POST names)')
     ap.add_argument('--max_frames', type=int, default=None)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--size', type=int, default=256)
@@ -335,8 +344,10 @@ def main(argv=None, prepare_model=None):
     if a.landmark_video == 'avi':
         os.makedirs(a.out, exist_ok=True)
         preview = os.path.join(a.out, 'landmark_seq2.avi')
-        write_landmark_avi(seq, preview, a.fps, device, a.audio, a.batch, a.size, a.landmark_video_size, a.landmark_video_quality)
+        write_landmark_avi(seq.cpu() if torch.is_tensor(seq) else seq, preview, a.fps, device, a.audio, a.batch, a.size, a.landmark_video_size, a.landmark_video_quality)
         print('landmark preview is', preview)
+    if torch.is_tensor(seq) and seq.is_cuda and a.triangulate == 'host':
+        seq = seq.cpu()                  # scipy triangulates per frame on the host: the sequence crosses once, here
     frames = stream.ClipStreamer(model, batch=a.batch, triangulate=a.triangulate).run(photo, lm0, seq, matte=matte)
     fdir = os.path.join(a.out, 'frames')
     if a.frames == 'png':

@@ -14,7 +14,9 @@ Mirrors of the reference's two networks, attribute for attribute, so that its ch
 Both run ONCE per clip over all windows: stock PyTorch-ROCm by default; ``set_lstm_backend('hip')`` (or
 APAMD_MODULE1_LSTM=hip) moves their LSTMs to the batched kernel of libapseq.so.  ``predict_landmarks_speaker_aware`` is ``Audio2landmark_model.test`` (train_audio2landmark.py:101-141,
 235-245, 247-309, 594-617) followed by the clip-level post-processing of main_end2end_module2.py:262-272; the simpler
-``predict_landmarks`` is the content branch alone (``__train_face_wo_pos__``).  NOT built: the AutoVC mel / speaker
+``predict_landmarks`` is the content branch alone (``__train_face_wo_pos__``).  That post-processing is numpy / scipy on the host
+by default; ``set_post_backend('device')`` (or APAMD_MODULE1_POST=device) runs it in libapseq.so (landmark_post.py) and keeps the
+landmark sequence on the GPU.  NOT built: the AutoVC mel / speaker
 embedding front end (librosa / pysptk / pyworld / resemblyzer are not in this image, and neither are the checkpoints);
 callers pass the (T, 18, 80) mel windows and the 256-d speaker embedding the reference's ``au_data`` / ``au_emb`` hold.
 """
@@ -54,6 +56,32 @@ def set_lstm_backend(name):
 
 def get_lstm_backend():
     return _lstm_backend
+
+
+# Who runs the clip-level post-processing between the networks and the frame loop: 'host' = numpy / scipy below (the
+# reference's own statements), 'device' = the apq_* calls of libapseq.so (landmark_post.py): the sequence then stays a CUDA
+# tensor from the mel windows on.  CPU tensors and CPU networks always take the host functions.
+POST_BACKENDS = ('host', 'device')
+
+
+def _checked_post_backend(name):
+    if name not in POST_BACKENDS:
+        raise ValueError('Module1 post-processing backend %r (known: %s)' % (name, ', '.join(POST_BACKENDS)))
+    return name
+
+
+_post_backend = _checked_post_backend(os.environ.get('APAMD_MODULE1_POST') or 'host')
+
+
+def set_post_backend(name):
+    """Select where the landmark post-processing runs; returns the previous backend."""
+    global _post_backend
+    prev, _post_backend = _post_backend, _checked_post_backend(name)
+    return prev
+
+
+def get_post_backend():
+    return _post_backend
 
 
 def _lstm_last(lstm, x):
@@ -303,6 +331,19 @@ def solve_inverse_lip(fl):
     return fl
 
 
+def blink_stamps(length, rng=np.random):
+    """The frames ``add_naive_eye`` blinks at in a clip of ``length`` frames (util/utils.py:373-380): 30, then steps of
+    60 + randint(30, 90) while they leave 16 frames behind them.  Draws from ``rng`` what the reference's loop draws."""
+    k2 = 15
+    stamps, t = [30], 30
+    while t < length - 1 - k2:
+        t += 60
+        t += rng.randint(30, 90)
+        if t < length - 1 - k2:
+            stamps.append(t)
+    return stamps
+
+
 def add_naive_eye(fl, rng=np.random):
     """util/utils.py:361-393 on (T, 68, C): eyelids slightly closed throughout, plus blinks at random times (the
     reference draws them from numpy's global generator)."""
@@ -311,13 +352,8 @@ def add_naive_eye(fl, rng=np.random):
     for a, b in pairs:
         fa, fb = fl[:, a].copy(), fl[:, b].copy()
         fl[:, a], fl[:, b] = r * fa + (1 - r) * fb, (1 - r) * fa + r * fb
-    k1, k2, length = 10, 15, fl.shape[0]
-    stamps, t = [30], 30
-    while t < length - 1 - k2:
-        t += 60
-        t += rng.randint(30, 90)
-        if t < length - 1 - k2:
-            stamps.append(t)
+    k1, k2 = 10, 15
+    stamps = blink_stamps(fl.shape[0], rng)
     lids = [37, 38, 40, 41, 43, 44, 46, 47]
     for t in stamps:
         for a, b in pairs:
@@ -339,13 +375,18 @@ def predict_landmarks_speaker_aware(net_g, net_c, au_windows, spk_emb, face_id, 
     au_windows (T, 18, 80), spk_emb (256,), face_id (204,) -> (T, 204) landmarks in Module1's normalised frame.
     Per 512-window segment: pose branch G (speaker embedding x 3, z = 0) -> Savitzky-Golay over the segment -> lips
     pulled together -> x amp_pos; content branch C on the first 18 frames -> calibrated; sum + face id; inverted-lip fix.
-    Then the nose-top extrapolation and a (5, 3) Savitzky-Golay over the clip."""
+    Then the nose-top extrapolation and a (5, 3) Savitzky-Golay over the clip.
+    With the 'device' post-processing backend and networks on the GPU the result is a (T, 204) CUDA tensor and nothing between
+    the windows and it touches the host; otherwise a numpy array."""
     net_g.eval()
     net_c.eval()
     dev = next(net_g.parameters()).device
     au = torch.as_tensor(au_windows, dtype=torch.float32, device=dev)
     emb = torch.as_tensor(spk_emb, dtype=torch.float32, device=dev).view(1, -1).expand(au.shape[0], -1)
     fid = torch.as_tensor(face_id, dtype=torch.float32, device=dev).view(1, FACE_ID_FEAT_SIZE)
+    if _post_backend == 'device' and dev.type == 'cuda':
+        return _speaker_aware_on_device(net_g, net_c, au, emb, fid, amp_pos, amp_lip_x, amp_lip_y, segment, smooth_win,
+                                        close_mouth_ratio)
     out = []
     for j in range(0, au.shape[0], segment):
         a, e = au[j:j + segment], emb[j:j + segment]
@@ -363,9 +404,37 @@ def predict_landmarks_speaker_aware(net_g, net_c, au_windows, spk_emb, face_id, 
     return _savgol(fl, 5)
 
 
+def _speaker_aware_on_device(net_g, net_c, au, emb, fid, amp_pos, amp_lip_x, amp_lip_y, segment, smooth_win, close_mouth_ratio):
+    """The loop of ``predict_landmarks_speaker_aware`` with every step behind the networks in libapseq.so: per segment one
+    Savitzky-Golay, one calibration and one assembly launch (lips closed, sum, inverted-lip fix, nose top) that writes the
+    segment's rows of the clip; then the clip's Savitzky-Golay.  Which segments are kept is known from the shapes."""
+    from . import landmark_post as lp
+    dev = au.device
+    lens = [min(segment, au.shape[0] - j) for j in range(0, au.shape[0], segment)]
+    fl = torch.empty((sum(n for n in lens if n >= 10), FACE_ID_FEAT_SIZE), dtype=torch.float32, device=dev)
+    if fl.shape[0] == 0:
+        raise ValueError('predict_landmarks_speaker_aware: no segment of at least 10 windows')
+    row = 0
+    for k, n in enumerate(lens):
+        if n < 10:                                                               # :288-289
+            continue
+        a, e = au[k * segment:k * segment + n], emb[k * segment:k * segment + n]
+        z = torch.zeros(n, 128, device=dev)
+        dis = net_g(a, e * 3.0, fid.repeat(n, 1), None, z)[0]
+        dis = lp.savgol(dis, int(min(n - 1, smooth_win) // 2 * 2 + 1))
+        base = lp.calib_baseline(net_c(a[:, 0:18, :], fid)[0], amp_lip_x, amp_lip_y)
+        lp.segment_assemble(dis, base, fid, close_mouth_ratio, amp_pos, close=True, lip=True, nose=True, out=fl[row:row + n])
+        row += n
+    return lp.savgol(fl, 5)
+
+
 def to_image_landmarks(fl, scale=1.0, shift=(0.0, 0.0), eyes=True, smooth=True, rng=np.random):
     """main_end2end_module2.py:262-272 on the (T, 204) output above: flip / scale / shift x and y into image pixels,
-    ``add_naive_eye``, the two clip-level Savitzky-Golay filters.  Returns (T, 68, 3)."""
+    ``add_naive_eye``, the two clip-level Savitzky-Golay filters.  Returns (T, 68, 3): a numpy array, or for a CUDA tensor a
+    CUDA tensor made by two launches of libapseq.so (the blink frames are drawn from ``rng`` on the host, as here)."""
+    if torch.is_tensor(fl) and fl.is_cuda:
+        from . import landmark_post as lp
+        return lp.to_image_landmarks(fl.float(), scale, shift, eyes, smooth, rng)
     fl = np.array(fl, dtype=np.float64).reshape((-1, 68, 3))
     fl[:, :, 0:2] = -fl[:, :, 0:2]
     fl[:, :, 0:2] = fl[:, :, 0:2] / scale - np.asarray(shift, dtype=np.float64)
@@ -378,7 +447,8 @@ def to_image_landmarks(fl, scale=1.0, shift=(0.0, 0.0), eyes=True, smooth=True, 
 def predict_landmarks(net, au_windows, face_id, scale=1.0, shift=(0.0, 0.0), segment=512, smooth=True):
     """Content branch only (``__train_face_wo_pos__``): segments of 512 windows through the content net
     (train_audio2landmark.py:279-296), ``fl = displacement + face_id`` (:298), then main_end2end_module2.py:264-271.
-    Returns (T, 68, 2) image-pixel landmarks (x, y)."""
+    Returns (T, 68, 2) image-pixel landmarks (x, y): a CUDA tensor with the 'device' post-processing backend and a network on
+    the GPU, else a numpy array."""
     net.eval()
     dev = next(net.parameters()).device
     au = torch.as_tensor(au_windows, dtype=torch.float32, device=dev)
@@ -387,7 +457,9 @@ def predict_landmarks(net, au_windows, face_id, scale=1.0, shift=(0.0, 0.0), seg
     for j in range(0, au.shape[0], segment):
         dis, f = net(au[j:j + segment][:, 0:18, :], fid)
         outs.append(dis + f)
-    fl = torch.cat(outs, 0).cpu().numpy()
+    fl = torch.cat(outs, 0)
+    if not (_post_backend == 'device' and fl.is_cuda):
+        fl = fl.cpu().numpy()
     return to_image_landmarks(fl, scale, shift, eyes=False, smooth=smooth)[:, :, :2]
 
 

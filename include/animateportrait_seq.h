@@ -1,7 +1,9 @@
 /*
  * animateportrait_seq.h -- C ABI of libapseq.so: the batched LSTM forward of Module1's two landmark networks
  * (Module1/src/models/model_audio2landmark.py:41-55 and :312-318: 3-layer LSTMs with 256 hidden units over up to 512
- * windows of 18 frames) on the MI355X (gfx950).
+ * windows of 18 frames) on the MI355X (gfx950), and the clip-level post-processing of their landmark sequence
+ * (train_audio2landmark.py:101-141, 235-309, 594-617 and main_end2end_module2.py:262-272): Savitzky-Golay smoothing,
+ * baseline calibration, segment assembly with the inverted-lip fix, the image transform with the eye lids.
  *
  * Like libapdata.so, libapstyle.so and libapface.so this library is NOT part of the model boundary
  * (include/animateportrait_amd.h, libapamd.so).  That one serves the batch-1 recurrence of the AutoVC converter
@@ -10,7 +12,8 @@
  *
  * Conventions: as in animateportrait_amd.h -- device pointers to contiguous fp32 tensors, caller-owned buffers, calls only
  * enqueue on `stream` (a hipStream_t as void*), 0 = ok, negative = error with a thread-local message (apq_last_error()).
- * A refused call launches nothing and writes nothing; apq_lstm_layer_fwd_ok needs no device.
+ * A refused call launches nothing and writes nothing; every launching call has a twin `<name>_ok` that needs no device.
+ * The post-processing entry points were added without a change of APQ_ABI_VERSION: nothing that existed changed.
  */
 #ifndef ANIMATEPORTRAIT_SEQ_H
 #define ANIMATEPORTRAIT_SEQ_H
@@ -53,6 +56,66 @@ int32_t apq_lstm_layer_fwd_ok(const float* x, const float* w_ih, const float* w_
                               const float* out, int32_t B, int32_t T, int32_t I, int32_t H, int32_t last_only);
 int apq_lstm_layer_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* out,
                        int32_t B, int32_t T, int32_t I, int32_t H, int32_t last_only, void* stream);
+
+/* ---------------------------------------------------------------- clip-level landmark post-processing (seq_post.hip)
+ * A landmark sequence is [T][204] fp32: 68 points x (x, y, z) per frame.  No call uses atomics, a workspace or a host
+ * synchronisation; all need 4-byte aligned pointers (APQ_ALIGN_ELEM).  Each `_ok` twin takes the launching call's
+ * arguments without the stream and returns 1 when the call is served, else 0 with the reason in apq_last_error(); it
+ * launches nothing and never dereferences a pointer.  The launching calls apply the same checks: APQ_ERR_INVALID for
+ * null pointers and empty or inconsistent sizes, APQ_ERR_UNSUPPORTED for sizes outside the served region and misaligned
+ * pointers. */
+#define APQ_LM_C 204            /* coordinates of a frame */
+#define APQ_SG_MIN_W 5          /* Savitzky-Golay window: odd, 5 .. 31, at most T */
+#define APQ_SG_MAX_W 31
+#define APQ_SEG_MAX_T 512       /* frames of a segment (apq_calib_baseline, apq_segment_assemble) */
+#define APQ_MAX_STAMPS 4096     /* blink stamps of apq_image_landmarks */
+
+/* Savitzky-Golay of order 3 along time on x [T][C] into y [T][C] (out of place), edges as scipy's mode='interp'.
+ * Columns [c0, c1) are filtered with window W0, columns [c1, c2) with W1; every other column of y stays untouched, and an
+ * empty range ignores its window and table.  0 <= c0 <= c1 <= c2 <= C.
+ * taps [(W / 2 + 1)][W]: row i < W / 2 gives output row i from the first W samples, x[0] first, and output row T - 1 - i
+ * from the last W samples, x[T - 1] first; row W / 2 holds the interior taps, x[t - W / 2] first.  (The rows are rows of the
+ * projector on cubics over W equidistant samples, which is symmetric under reversal of both indices.) */
+int32_t apq_savgol_ok(const float* x, const float* y, const float* taps0, const float* taps1, int32_t T, int32_t C,
+                      int32_t c0, int32_t c1, int32_t c2, int32_t W0, int32_t W1);
+int apq_savgol(const float* x, float* y, const float* taps0, const float* taps1, int32_t T, int32_t C, int32_t c0, int32_t c1,
+               int32_t c2, int32_t W0, int32_t W1, void* stream);
+
+/* __calib_baseline_pred_fls__ on x [T][204] into y [T][204] (out of place): per column subtract the mean of its k smallest
+ * values, then multiply the mouth's x columns (144, 147, ...) by amp_x and its y columns (145, 148, ...) by amp_y.
+ * 2 <= T <= APQ_SEG_MAX_T, 1 <= k < T.  Only the sum of the k smallest is used, so ties do not matter. */
+int32_t apq_calib_baseline_ok(const float* x, const float* y, int32_t T, int32_t k, float amp_x, float amp_y);
+int apq_calib_baseline(const float* x, float* y, int32_t T, int32_t k, float amp_x, float amp_y, void* stream);
+
+/* One segment, in [T][204] -> out [T][204] (out of place), 1 <= T <= APQ_SEG_MAX_T; `flags` selects the steps, in this order:
+ *   APQ_SEG_CLOSE  close_pose_branch_mouth(in, ratio), then x amp, then + base [T][204] + fid [204] when both are given
+ *                  (base and fid: both or neither);
+ *   APQ_SEG_LIP    __solve_inverse_lip2__: the frames whose inner-lip polygon (points 60..67) has a negative area get
+ *                  their inner lip closed and their outer-lip y moved along with the frame before, which is already fixed;
+ *   APQ_SEG_NOSE   point 27 = 2 x point 28 - point 29.
+ * All in fp32 in the operation order of the numpy statements (no fused multiply-add). */
+#define APQ_SEG_CLOSE 1
+#define APQ_SEG_LIP 2
+#define APQ_SEG_NOSE 4
+int32_t apq_segment_assemble_ok(const float* in, const float* base, const float* fid, const float* out, int32_t T, double ratio,
+                                float amp, int32_t flags);
+int apq_segment_assemble(const float* in, const float* base, const float* fid, float* out, int32_t T, double ratio, float amp,
+                         int32_t flags, void* stream);
+
+/* main_end2end_module2.py:262-266 on in [T][204] -> out [T][204] (out of place), 1 <= T <= APQ_MAX_T:
+ *   APQ_IMG_TRANSFORM  x, y -> -x / scale - shift_x, -y / scale - shift_y (z untouched);
+ *   APQ_IMG_EYES       add_naive_eye: the 0.95 / 0.05 lid mix on every frame, then a blink at each of the n_stamps frames in
+ *                      stamps (int32, device).  A blink at t rewrites the frames t - 9 .. t + 14 from t - 10, t and t + 15,
+ *                      so the call asks for T >= 46 and 1 <= n_stamps <= APQ_MAX_STAMPS; the stamps must be at least 25 apart
+ *                      and in [10, T - 16], which the call cannot check: frames outside the sequence are never read (their
+ *                      index is clamped), but such a blink is not the reference's.
+ * Without APQ_IMG_EYES stamps may be null. */
+#define APQ_IMG_TRANSFORM 1
+#define APQ_IMG_EYES 2
+int32_t apq_image_landmarks_ok(const float* in, const float* out, const int32_t* stamps, int32_t n_stamps, int32_t T, double scale,
+                               double shift_x, double shift_y, int32_t flags);
+int apq_image_landmarks(const float* in, float* out, const int32_t* stamps, int32_t n_stamps, int32_t T, double scale,
+                        double shift_x, double shift_y, int32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,13 @@ LSTM backends in ONE process, in alternated rounds, and split into
 Medians over the rounds are reported.  Then the kernel alone: one apq_lstm_layer_fwd launch at B = 512, T = 18 and
 I in {80, 161, 256} between device events, next to a one-layer nn.LSTM of the same shape.
 
-    python tools/bench_module1.py --out profiles/module1_lstm.json
+Then the post-processing backends (module1.set_post_backend: 'host' = numpy / scipy, 'device' = the apq_* calls of libapseq.so),
+again alternated in the same process on the same windows, LSTM backend as configured: the stage split as above (for 'device' the
+rest is launches and kernels instead of host work), ``to_image_landmarks`` on the stage's output as a line of its own (it is not
+part of the stage time above), and both once more with the networks unwrapped -- no synchronise inside the stage, the time a
+clip sees.
+
+    python tools/bench_module1.py --out profiles/module1_lstm.json --post_out profiles/module1_post.json
 
 Needs a GPU: there is no CPU mode, a time taken without the device would say nothing."""
 import argparse
@@ -51,6 +57,54 @@ def stage_once(m1, pose, content, au, spk, fid):
     total = time.perf_counter() - t0
     nets = pose.seconds + content.seconds
     return fl, {'total': total, 'networks': nets, 'host': total - nets, 'pose_net': pose.seconds, 'content_net': content.seconds}
+
+
+def post_once(m1, pose, content, au, spk, fid):
+    """One stage + to_image_landmarks: split (networks wrapped in ``Timed``) and unsplit (the bare networks)."""
+    fl, t = stage_once(m1, pose, content, au, spk, fid)
+    t['rest'] = t.pop('host')            # everything outside the networks: host work, or launches and kernels
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    img = m1.to_image_landmarks(fl, scale=0.01, shift=(-128.0, -128.0), rng=np.random.RandomState(0))
+    torch.cuda.synchronize()
+    t['to_image_landmarks'] = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fl2 = m1.predict_landmarks_speaker_aware(pose.net, content.net, au, spk, fid)
+    torch.cuda.synchronize()
+    t['stage_unsplit'] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    m1.to_image_landmarks(fl2, scale=0.01, shift=(-128.0, -128.0), rng=np.random.RandomState(0))
+    torch.cuda.synchronize()
+    t['stage_and_image_unsplit'] = t['stage_unsplit'] + time.perf_counter() - t0
+    return fl, img, t
+
+
+def _medians(times):
+    return {k: {'median': 1e3 * statistics.median(t[k] for t in times), 'min': 1e3 * min(t[k] for t in times),
+                'max': 1e3 * max(t[k] for t in times)} for k in times[0]}
+
+
+def post_rounds(m1, pose, content, au, spk, fid, rounds, warmup):
+    backends = ('host', 'device')
+    prev = m1.get_post_backend()
+    times, outs = {b: [] for b in backends}, {}
+    try:
+        for r in range(warmup + rounds):
+            for b in (backends if r % 2 == 0 else backends[::-1]):
+                m1.set_post_backend(b)
+                fl, img, t = post_once(m1, pose, content, au, spk, fid)
+                outs[b] = (np.asarray(fl.cpu() if torch.is_tensor(fl) else fl), np.asarray(img.cpu() if torch.is_tensor(img) else img))
+                if r >= warmup:
+                    times[b].append(t)
+    finally:
+        m1.set_post_backend(prev)
+    res = {b: _medians(times[b]) for b in backends}
+    res['lstm_backend'] = m1.get_lstm_backend()
+    res['landmarks_linf_device_vs_host'] = float(np.abs(outs['device'][0] - outs['host'][0]).max())
+    res['landmarks_range'] = float(np.abs(outs['host'][0]).max())
+    res['image_landmarks_linf_device_vs_host_px'] = float(np.abs(outs['device'][1] - outs['host'][1]).max())
+    return res
 
 
 def kernel_times(dev, reps):
@@ -99,6 +153,7 @@ def main(argv=None):
     ap.add_argument('--kernel_reps', type=int, default=20)
     ap.add_argument('--frames', type=int, default=625)
     ap.add_argument('--out', default=None, help='write the result as JSON here as well')
+    ap.add_argument('--post_out', default=None, help='write the post-processing backends\' part of the result as JSON here')
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('bench_module1: no GPU')
@@ -132,8 +187,15 @@ def main(argv=None):
     res['landmarks_linf_hip_vs_library'] = float(np.abs(fls['hip'] - fls['library']).max())
     res['landmarks_range'] = float(np.abs(fls['library']).max())
     res['kernel_per_layer'] = kernel_times(dev, a.kernel_reps)
+    post = {k: res[k] for k in ('device', 'windows', 'segments', 'rounds', 'warmup', 'unit')}
+    post['post'] = post_rounds(m1, pose, content, au, spk, fid, a.rounds, a.warmup)
+    res['post'] = post['post']
     text = json.dumps(res, indent=1)
     print(text)
+    if a.post_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.post_out)), exist_ok=True)
+        with open(a.post_out, 'w') as f:
+            f.write(json.dumps(post, indent=1) + '\n')
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, 'w') as f:
