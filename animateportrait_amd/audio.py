@@ -13,9 +13,9 @@ Host-side numpy / scipy, as in the reference (the mel stage runs once per clip o
     (Module1/src/dataset/audio2landmark/audio2landmark_dataset.py:73-78): windows ``au[i : i + 18]`` for
     ``i in range(0, T - 18, 1)``.
 The AutoVC content converter between the mel spectrogram and the windows (``Generator(16, 256, 512, 16)``, :205-208) lives in
-``autovc.py`` (round 4) and enters ``clip_audio_features`` as the ``converter`` callable.  NOT here, because the packages are
-not in this image: the RAPT f0 track the converter consumes (pysptk) and the speaker embedding (resemblyzer) -- both are
-arguments of ``autovc.convert_mel``.
+``autovc.py`` (round 4) and enters ``clip_audio_features`` as the ``converter`` callable.  NOT here: the speaker embedding
+(resemblyzer, not in this image), an argument of ``autovc.convert_mel``; its other argument, the f0 track (pysptk's RAPT in the
+reference), comes from a file or from ``f0.py``, which tracks it on the device from ``conditioned_signal``.
 The mel filter bank restates librosa 0.7's ``filters.mel`` (Slaney scale, Slaney area normalisation, the version the
 reference pins); librosa is absent from this image, so that table is **parity unpinned** -- everything around it is pinned
 to the reference's own function (tests/golden/make_audio_golden.py).
@@ -106,8 +106,10 @@ def stft_magnitude(x, n_fft=N_FFT, hop=HOP):
     return np.abs(np.fft.rfft(frames * win, n=n_fft, axis=1))
 
 
-def mel_spectrogram(x, mel_basis=None):
-    """x: samples at 16 kHz, (T,) or (T, channels) -> S (frames, 80) float64 in about [0, 1]."""
+def conditioned_signal(x):
+    """x: samples at 16 kHz, (T,) or (T, channels) -> ``wav`` of extract_f0_func_audiofile (:109-114), float64: first channel,
+    the 1e-6 sample appended when the length is a multiple of 256, the high-pass run forward-backward, x 0.95 + dither.  Both the
+    mel spectrogram and the f0 tracker (f0.py, which reads ``float32(wav) * 32768``) start from it."""
     x = np.asarray(x, dtype=np.float64)
     if x.ndim >= 2:
         x = x[:, 0]
@@ -115,7 +117,12 @@ def mel_spectrogram(x, mel_basis=None):
         x = np.concatenate((x, np.array([1e-06])), axis=0)
     b, a = signal.butter(5, 30.0 / (0.5 * SAMPLE_RATE), btype='high', analog=False)
     y = signal.filtfilt(b, a, x)
-    wav = y * 0.95 + (np.random.RandomState(0).rand(y.shape[0]) - 0.5) * 1e-06
+    return y * 0.95 + (np.random.RandomState(0).rand(y.shape[0]) - 0.5) * 1e-06
+
+
+def mel_spectrogram(x, mel_basis=None):
+    """x: samples at 16 kHz, (T,) or (T, channels) -> S (frames, 80) float64 in about [0, 1]."""
+    wav = conditioned_signal(x)
     basis = mel_filterbank() if mel_basis is None else mel_basis
     d_mel = np.dot(stft_magnitude(wav), basis.T)
     min_level = np.exp(-100 / 20 * np.log(10))

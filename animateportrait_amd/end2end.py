@@ -91,6 +91,11 @@ def landmarks_from_audio(a, device):
         G = autovc.load_generator(a.load_AUTOVC_name, device)
         emb_trg = autovc.load_target_embedding(a.autovc_target_emb)
         f0 = np.load(a.f0_npy) if a.f0_npy else None
+        if a.f0 == 'device':
+            # the track of the samples clip_audio_features conditions: read, resample, loudness (f0.py conditions them itself)
+            from . import f0 as f0_device
+            x, sr = audio.read_wav(a.wav)
+            f0 = f0_device.f0_track(audio.normalize_loudness(audio.resample_to_16k(x, sr)), a.f0_gender, device)
         if f0 is None:
             print('WARNING: no --f0_npy: the converter runs on an all-unvoiced f0 track (the reference extracts RAPT f0 with '
                   'pysptk, which is not in this image)')
@@ -125,6 +130,11 @@ def make_parser():
                     help='AutoVC converter checkpoint (main_end2end_module2.py:43); Module1 is fed the converted spectrogram')
     ap.add_argument('--autovc_target_emb', default=None, help='target-speaker embedding txt (default: the reference checkout\'s obama_emb.txt)')
     ap.add_argument('--f0_npy', default=None, help='normalised RAPT f0 track of the clip (extract_f0_func_audiofile), one value per mel frame')
+    ap.add_argument('--f0', choices=('npy', 'device'), default=None,
+                    help='where the converter\'s f0 track comes from: npy = the file --f0_npy names, device = tracked from --wav on '
+                         'the GPU (f0.py: RAPT as published, libapseq.so); default: --f0_npy when given, else an all-unvoiced track')
+    ap.add_argument('--f0_gender', choices=('F', 'M'), default='F',
+                    help='with --f0 device: the search range, F = 100 .. 600 Hz (what the reference\'s converter passes), M = 50 .. 250 Hz')
     ap.add_argument('--no_autovc', action='store_true',
                     help='feed the RAW mel spectrogram to Module1 (NOT what the reference does: its checkpoints were trained on '
                          'AutoVC-converted spectrograms); for experiments with networks trained that way')
@@ -298,6 +308,12 @@ def main(argv=None, prepare_model=None):
     if a.wav is not None and a.speaker_emb is None:
         ap.error('--wav needs --speaker_emb (the 256-d resemblyzer embedding the speaker-aware branch is conditioned on, '
                  'main_end2end_module2.py:215-217); a zero vector is not a neutral default')
+    if a.f0 == 'device' and a.f0_npy is not None:
+        ap.error('--f0 device tracks the f0 from --wav: it does not go with --f0_npy')
+    if a.f0 == 'npy' and a.f0_npy is None:
+        ap.error('--f0 npy needs --f0_npy')
+    if a.f0 == 'device' and (a.wav is None or a.no_autovc):
+        ap.error('--f0 device: the track feeds the AutoVC converter of --wav (it needs --wav, without --no_autovc)')
     if a.frames == 'none' and a.video != 'avi':
         ap.error('--frames none leaves nothing to assemble: it needs --video avi')
     if not 1 <= a.video_quality <= 100:

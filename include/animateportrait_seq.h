@@ -117,6 +117,41 @@ int32_t apq_image_landmarks_ok(const float* in, const float* out, const int32_t*
 int apq_image_landmarks(const float* in, float* out, const int32_t* stamps, int32_t n_stamps, int32_t T, double scale,
                         double shift_x, double shift_y, int32_t flags, void* stream);
 
+/* ------------------------------------------------------------------------------- the clip's f0 track (seq_f0.hip)
+ * RAPT (Talkin 1995, the get_f0 defaults) with one NCCF pass at the full rate, as tests/f0_reference.py states it in float64:
+ * apq_f0_candidates makes every frame's table (one workgroup per frame, no frame reads another's results), apq_f0_track runs
+ * the dynamic programme, the backtrack and speaker_normalization in one workgroup.  One launch each, no atomics, no host
+ * synchronisation, no workspace beyond the caller's tensors below; 4-byte aligned pointers (APQ_ALIGN_ELEM; the byte tensors
+ * need none).  The `_ok` twins and the error codes follow the rules of the post-processing calls above.  Added without a change
+ * of APQ_ABI_VERSION: nothing that existed changed. */
+#define APQ_F0_HOP 256          /* samples between frames: frame t is centred on sample 256 t */
+#define APQ_F0_CANDS 19         /* voiced hypotheses kept per frame */
+#define APQ_F0_STATES 20        /* ... plus the unvoiced one */
+#define APQ_F0_MIN_LAG 2        /* kmin >= 2 (phi is evaluated from kmin - 1 on) */
+#define APQ_F0_MAX_LAG 320      /* kmax <= 320 (16 kHz / 50 Hz) */
+#define APQ_F0_UNVOICED 255     /* path entry of an unvoiced frame */
+
+/* x [L]: the signal on the 16-bit scale (float32(wav) * 32768), L >= 1, any length; frames t = 0 .. T - 1, 1 <= T <= APQ_MAX_T
+ * (the mel's frame count is L / 256 + 1; samples outside [0, L) read as zero, so a frame may lie wholly past the signal).
+ * APQ_F0_MIN_LAG <= kmin <= kmax <= APQ_F0_MAX_LAG.  Written per frame:
+ *   count [T] int32        candidates kept, 0 .. 19
+ *   lag, val [T][19]       their refined lags (samples, ascending) and NCCF values; zero behind count
+ *   rr [T], s [T]          the rms ratio and the spectral stationarity term of the transition costs (frame 0: 1, 1) */
+int32_t apq_f0_candidates_ok(const float* x, int32_t L, int32_t T, int32_t kmin, int32_t kmax, const int32_t* count,
+                             const float* lag, const float* val, const float* rr, const float* s);
+int apq_f0_candidates(const float* x, int32_t L, int32_t T, int32_t kmin, int32_t kmax, int32_t* count, float* lag, float* val,
+                      float* rr, float* s, void* stream);
+
+/* The dynamic programme over the tables of apq_f0_candidates (a count outside 0 .. 19 is clamped), fs > 0 the sample rate:
+ *   back [T][20] uint8     best predecessor state of every state (states: the candidates, then the unvoiced hypothesis)
+ *   path [T] uint8         the chosen candidate of every frame, APQ_F0_UNVOICED where unvoiced
+ *   f0 [T]                 f0_norm: (clip((ln(fs / lag) - mean) / std / 4, -1, 1) + 1) / 2 on voiced frames, -1e10 on unvoiced
+ *                          ones; no voiced frame: all -1e10; std = 0: voiced frames get 0.5 */
+int32_t apq_f0_track_ok(const int32_t* count, const float* lag, const float* val, const float* rr, const float* s, int32_t T,
+                        int32_t kmax, double fs, const uint8_t* back, const uint8_t* path, const float* f0);
+int apq_f0_track(const int32_t* count, const float* lag, const float* val, const float* rr, const float* s, int32_t T,
+                 int32_t kmax, double fs, uint8_t* back, uint8_t* path, float* f0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
