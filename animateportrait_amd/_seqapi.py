@@ -1,5 +1,6 @@
 """ctypes binding of libapseq.so (C ABI declared in include/animateportrait_seq.h): the batched LSTM forward of Module1's
-landmark networks, the clip-level post-processing of their landmark sequence and the clip's f0 track (f0.py).  Separate from _capi.py / libapamd.so, the boundary a model integrator binds.
+landmark networks, the clip-level post-processing of their landmark sequence, the clip's f0 track (f0.py) and the two ends of
+its speaker embedding (speaker.py).  Separate from _capi.py / libapamd.so, the boundary a model integrator binds.
 Loaded on first use; as there, a missing library or a failed call raises -- there is no silent fallback."""
 import ctypes
 import os
@@ -18,6 +19,7 @@ LM_C, SG_MIN_W, SG_MAX_W, SEG_MAX_T, MAX_STAMPS = 204, 5, 31, 512, 4096
 SEG_CLOSE, SEG_LIP, SEG_NOSE = 1, 2, 4
 IMG_TRANSFORM, IMG_EYES = 1, 2
 F0_HOP, F0_CANDS, F0_STATES, F0_MIN_LAG, F0_MAX_LAG, F0_UNVOICED = 256, 19, 20, 2, 320, 255
+MEL_MIN_FFT, MEL_MAX_FFT, MEL_MAX_MELS, ALIGN_F64, SPK_E, SPK_MAX_B = 16, 1024, 128, 8, 256, 4096
 
 _i32, _ptr, _f32, _f64 = ctypes.c_int32, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
 # name -> (restype, argtypes); every symbol include/animateportrait_seq.h declares
@@ -40,6 +42,11 @@ SIGNATURES = {
     'apq_f0_candidates': (ctypes.c_int, [_ptr] + [_i32] * 4 + [_ptr] * 5 + [_ptr]),
     'apq_f0_track_ok': (_i32, [_ptr] * 5 + [_i32, _i32, _f64] + [_ptr] * 3),
     'apq_f0_track': (ctypes.c_int, [_ptr] * 5 + [_i32, _i32, _f64] + [_ptr] * 3 + [_ptr]),
+    # the clip's speaker embedding (speaker.py)
+    'apq_mel_frames_ok': (_i32, [_ptr] * 4 + [_i32] * 5),
+    'apq_mel_frames': (ctypes.c_int, [_ptr] * 4 + [_i32] * 5 + [_ptr]),
+    'apq_speaker_head_ok': (_i32, [_ptr] * 5 + [_i32]),
+    'apq_speaker_head': (ctypes.c_int, [_ptr] * 5 + [_i32] + [_ptr]),
 }
 
 _lib = None

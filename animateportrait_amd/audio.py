@@ -13,9 +13,10 @@ Host-side numpy / scipy, as in the reference (the mel stage runs once per clip o
     (Module1/src/dataset/audio2landmark/audio2landmark_dataset.py:73-78): windows ``au[i : i + 18]`` for
     ``i in range(0, T - 18, 1)``.
 The AutoVC content converter between the mel spectrogram and the windows (``Generator(16, 256, 512, 16)``, :205-208) lives in
-``autovc.py`` (round 4) and enters ``clip_audio_features`` as the ``converter`` callable.  NOT here: the speaker embedding
-(resemblyzer, not in this image), an argument of ``autovc.convert_mel``; its other argument, the f0 track (pysptk's RAPT in the
-reference), comes from a file or from ``f0.py``, which tracks it on the device from ``conditioned_signal``.
+``autovc.py`` (round 4) and enters ``clip_audio_features`` as the ``converter`` callable.  Its two other arguments are made
+elsewhere: the speaker embedding (resemblyzer in the reference) comes from a txt or from ``speaker.py``, which embeds the clip on the
+device and uses ``read_wav``, ``resample_to_16k`` and ``mel_filterbank`` from here; the f0 track (pysptk's RAPT in the reference) comes
+from a file or from ``f0.py``, which tracks it on the device from ``conditioned_signal``.
 The mel filter bank restates librosa 0.7's ``filters.mel`` (Slaney scale, Slaney area normalisation, the version the
 reference pins); librosa is absent from this image, so that table is **parity unpinned** -- everything around it is pinned
 to the reference's own function (tests/golden/make_audio_golden.py).

@@ -17,8 +17,8 @@ for a 256-px photo -> ``--landmark_scale 0.5``), ``--landmarks_npy FILE`` ((T + 
 itself: ``--wav FILE --photo_landmarks TXT`` runs the audio half of main_end2end_module2.py:181-272 in process -- mel
 windows (audio.py) -> the two Module1 networks (``--load_a2l_G_name`` / ``--load_a2l_C_name`` checkpoints) -> the landmark
 post-processing -> image-pixel landmarks -- with the photo's detected (68, 3) landmarks (``face_alignment`` output, a txt of 68
-rows) and a speaker embedding (``--speaker_emb`` txt of 256 numbers; the resemblyzer / AutoVC front end is not part of this
-build) as inputs.  The matte comes from ``--matte PNG`` (white = foreground) unless the model has its matting network.
+rows) and a speaker embedding as inputs: ``--speaker_emb`` txt of 256 numbers, or ``--speaker_emb_from wav --speaker_encoder
+CKPT``, which embeds ``--wav`` on the device (speaker.py: resemblyzer's encoder restated, without its silence trim).  The matte comes from ``--matte PNG`` (white = foreground) unless the model has its matting network.
 """
 import argparse
 import os
@@ -83,7 +83,13 @@ def landmarks_from_audio(a, device):
         module1.set_lstm_backend(a.module1_lstm)
     if a.module1_post is not None:
         module1.set_post_backend(a.module1_post)
-    emb = np.loadtxt(a.speaker_emb).reshape(-1).astype(np.float32)
+    if a.speaker_emb_from == 'wav':
+        # main_end2end_module2.py:216-219: the clip's own embedding, before the converter; it conditions both stages below
+        from . import speaker
+        x, sr = audio.read_wav(a.wav)
+        emb = speaker.speaker_embedding(x, sr, speaker.load_encoder(a.speaker_encoder, device))
+    else:
+        emb = np.loadtxt(a.speaker_emb).reshape(-1).astype(np.float32)
     converter = None
     if not a.no_autovc:
         # main_end2end_module2.py:218-224: Module1 sees the AutoVC-converted spectrogram, not the raw mel
@@ -126,6 +132,11 @@ def make_parser():
     ap.add_argument('--wav', default=None, help='drive the clip from this audio file (needs --photo_landmarks)')
     ap.add_argument('--photo_landmarks', default=None, help='txt, 68 rows "x y z": the photo\'s detected landmarks in pixels')
     ap.add_argument('--speaker_emb', default=None, help='txt with the 256-d resemblyzer speaker embedding of the clip (required with --wav)')
+    ap.add_argument('--speaker_emb_from', choices=('txt', 'wav'), default=None,
+                    help='where the speaker embedding comes from: txt = the file --speaker_emb names, wav = computed from --wav on the '
+                         'GPU with the encoder --speaker_encoder names (speaker.py, libapseq.so; long silences are not trimmed as '
+                         'resemblyzer trims them); default: txt')
+    ap.add_argument('--speaker_encoder', default=None, help="with --speaker_emb_from wav: resemblyzer's pretrained.pt")
     ap.add_argument('--load_AUTOVC_name', default='Module1/checkpoints/ckpt_autovc.pth',
                     help='AutoVC converter checkpoint (main_end2end_module2.py:43); Module1 is fed the converted spectrogram')
     ap.add_argument('--autovc_target_emb', default=None, help='target-speaker embedding txt (default: the reference checkout\'s obama_emb.txt)')
@@ -305,7 +316,16 @@ def main(argv=None, prepare_model=None):
         ap.error('exactly one of --landmarks / --landmarks_npy / --wav')
     if a.wav is not None and a.photo_landmarks is None:
         ap.error('--wav needs --photo_landmarks')
-    if a.wav is not None and a.speaker_emb is None:
+    if a.speaker_emb_from == 'wav':
+        if a.speaker_emb is not None:
+            ap.error('--speaker_emb_from wav computes the embedding from --wav: it does not go with --speaker_emb')
+        if a.wav is None:
+            ap.error('--speaker_emb_from wav needs --wav')
+        if a.speaker_encoder is None:
+            ap.error('--speaker_emb_from wav needs --speaker_encoder (resemblyzer\'s pretrained.pt)')
+    elif a.speaker_encoder is not None:
+        ap.error('--speaker_encoder goes with --speaker_emb_from wav')
+    if a.wav is not None and a.speaker_emb is None and a.speaker_emb_from != 'wav':
         ap.error('--wav needs --speaker_emb (the 256-d resemblyzer embedding the speaker-aware branch is conditioned on, '
                  'main_end2end_module2.py:215-217); a zero vector is not a neutral default')
     if a.f0 == 'device' and a.f0_npy is not None:

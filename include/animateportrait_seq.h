@@ -13,7 +13,8 @@
  * Conventions: as in animateportrait_amd.h -- device pointers to contiguous fp32 tensors, caller-owned buffers, calls only
  * enqueue on `stream` (a hipStream_t as void*), 0 = ok, negative = error with a thread-local message (apq_last_error()).
  * A refused call launches nothing and writes nothing; every launching call has a twin `<name>_ok` that needs no device.
- * The post-processing entry points were added without a change of APQ_ABI_VERSION: nothing that existed changed.
+ * The post-processing entry points were added without a change of APQ_ABI_VERSION: nothing that existed changed; so were the
+ * clip's f0 track and the two ends of its speaker embedding (further down).
  */
 #ifndef ANIMATEPORTRAIT_SEQ_H
 #define ANIMATEPORTRAIT_SEQ_H
@@ -151,6 +152,41 @@ int32_t apq_f0_track_ok(const int32_t* count, const float* lag, const float* val
                         int32_t kmax, double fs, const uint8_t* back, const uint8_t* path, const float* f0);
 int apq_f0_track(const int32_t* count, const float* lag, const float* val, const float* rr, const float* s, int32_t T,
                  int32_t kmax, double fs, uint8_t* back, uint8_t* path, float* f0, void* stream);
+
+/* ------------------------------------------------------------------------- the clip's speaker embedding (seq_speaker.hip)
+ * The two ends of resemblyzer's VoiceEncoder as tests/speaker_reference.py states them in float64; its three LSTM layers of 256
+ * hidden units lie between them (apq_lstm_layer_fwd or the library's).  One launch each, no atomics, no workspace, no host
+ * synchronisation.  The `_ok` twins and the error codes follow the rules of the post-processing calls above.  Added without a
+ * change of APQ_ABI_VERSION: nothing that existed changed. */
+#define APQ_MEL_MIN_FFT 16      /* n_fft: even, 16 .. 1024, a power of two or not */
+#define APQ_MEL_MAX_FFT 1024
+#define APQ_MEL_MAX_MELS 128    /* rows of the filter bank */
+#define APQ_ALIGN_F64 8         /* alignment in bytes of the fp64 window */
+#define APQ_SPK_E 256           /* width of the embedding (= APQ_LSTM_H) */
+#define APQ_SPK_MAX_B 4096      /* windows of an utterance */
+
+/* Mel frames of a centred short-time Fourier transform:
+ *   x [L] fp32 samples, window [n_fft] fp64, basis [n_mels][n_fft / 2 + 1] fp32  ->  out [T][n_mels] fp32, T = L / hop + 1
+ * Frame t is the n_fft samples centred on sample t hop of the reflect-padded signal (numpy's 'reflect': the edge sample is not
+ * repeated; n_fft / 2 samples on each side).  Per frame: times window, the DFT bins 0 .. n_fft / 2, |X|^power (power 1 or 2),
+ * times basis.  All of it is carried in fp64 and rounded to fp32 once, at the store.
+ * Served: n_fft even in [APQ_MEL_MIN_FFT, APQ_MEL_MAX_FFT], 1 <= hop <= n_fft, 1 <= n_mels <= APQ_MEL_MAX_MELS,
+ * L > n_fft / 2 (one reflection reaches every sample a frame reads), T <= APQ_MAX_T.  x, basis and out 4-byte aligned
+ * (APQ_ALIGN_ELEM), window 8-byte aligned (APQ_ALIGN_F64). */
+int32_t apq_mel_frames_ok(const float* x, const double* window, const float* basis, const float* out, int32_t L, int32_t n_fft,
+                          int32_t hop, int32_t n_mels, int32_t power);
+int apq_mel_frames(const float* x, const double* window, const float* basis, float* out, int32_t L, int32_t n_fft, int32_t hop,
+                   int32_t n_mels, int32_t power, void* stream);
+
+/* The encoder's head on h [B][256], the last LSTM layer's h_{T-1} of every window; w [256][256] (rows = outputs), b [256]:
+ *   partial [B][256]  relu(w h + b) divided by its L2 norm, per row
+ *   embed [256]       the mean of the partial rows divided by its L2 norm
+ * The products are fp32 (four runs of 64 fused multiply-adds per output, added as (0 + 1) + (2 + 3), then + b); the norms and the
+ * mean are accumulated in fp64 in a fixed order (the mean over the unrounded quotients, row 0 first), so the result does not
+ * depend on scheduling.  A row whose ReLU output is all zero stays zero and still counts in the mean; when every row is zero,
+ * embed is zero (the reference's arithmetic gives 0 / 0 in both places).  1 <= B <= APQ_SPK_MAX_B; 4-byte aligned pointers. */
+int32_t apq_speaker_head_ok(const float* h, const float* w, const float* b, const float* partial, const float* embed, int32_t B);
+int apq_speaker_head(const float* h, const float* w, const float* b, float* partial, float* embed, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
