@@ -15,6 +15,9 @@ OVF_LEVEL, OVF_MERGED, OVF_STAGE = 1, 2, 4
 PNET_PARAMS, RNET_PARAMS, ONET_PARAMS = 6632, 100178, 389040
 NMS_UNION, NMS_MIN = 0, 1
 NET_R, NET_O = 0, 1
+FAN_POINTS, FAN_MAX_RES, FAN_MAX_B = 68, 1024, 16
+FAN_RGB, FAN_BGR = 0, 1
+ERR_INVALID, ERR_UNSUPPORTED = -1, -2
 
 _i32, _i64, _ptr, _f32, _f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
 # name -> (restype, argtypes); every symbol include/animateportrait_face.h declares
@@ -38,6 +41,10 @@ SIGNATURES = {
     'apf_net': (ctypes.c_int, [_i32, _ptr, _ptr, _i32] + [_ptr] * 6),
     'apf_crop_resize_cubic_ok': (_i32, [_ptr] + [_i32] * 6 + [_ptr]),
     'apf_crop_resize_cubic': (ctypes.c_int, [_ptr] + [_i32] * 7 + [_ptr] * 2),
+    'apf_fan_crop_ok': (_i32, [_ptr, _i32, _i32] + [_f64] * 4 + [_i32] * 3 + [_ptr]),
+    'apf_fan_crop': (ctypes.c_int, [_ptr, _i32, _i32] + [_f64] * 4 + [_i32] * 3 + [_ptr] * 2),
+    'apf_fan_decode_ok': (_i32, [_ptr, _ptr, _i32, _i32, _ptr, _ptr]),
+    'apf_fan_decode': (ctypes.c_int, [_ptr, _ptr, _i32, _i32, _ptr, _i32, _ptr, _ptr]),
 }
 
 _lib = None

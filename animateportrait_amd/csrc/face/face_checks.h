@@ -151,4 +151,64 @@ inline int check_crop_resize_cubic(const void* img, int H, int W, int x0, int y0
     return APF_OK;
 }
 
+// ---- FAN: box -> centre and scale -> the inverse transform's coefficients (the header states the order; nothing is fused:
+// the face library is built with -ffp-contract=off, on the host as on the device)
+struct FanFrame {
+    double i00, i02x, i02y;        // X = i00 * px + i02x,  Y = i00 * py + i02y
+};
+
+inline bool fan_box_ok(double x0, double y0, double x1, double y1) {
+    const double lim = 4.0 * APF_MAX_SIDE;
+    // (sides from 1e-6 px: below that the transform's coefficients leave the range in which they are finite)
+    return x1 - x0 >= 1e-6 && y1 - y0 >= 1e-6 && x0 >= -lim && y0 >= -lim && x1 <= lim && y1 <= lim;      // (false for a NaN)
+}
+
+inline FanFrame fan_frame(double x0, double y0, double x1, double y1, int S) {
+    const double cx = x1 - (x1 - x0) / 2.0;
+    const double cy = y1 - (y1 - y0) / 2.0 - (y1 - y0) * 0.12;
+    const double scale = (x1 - x0 + y1 - y0) / 195.0;
+    const double h = 200.0 * scale;
+    const double a = (double)S / h;
+    const double bx = (double)S * (0.5 - cx / h), by = (double)S * (0.5 - cy / h);
+    return FanFrame{1.0 / a, -bx / a, -by / a};
+}
+
+struct FanWindow {
+    int ulx, uly, w, h;
+};
+
+inline FanWindow fan_window(double x0, double y0, double x1, double y1, int R) {
+    const FanFrame f = fan_frame(x0, y0, x1, y1, R);
+    const int ulx = (int)(f.i00 * 1.0 + f.i02x), uly = (int)(f.i00 * 1.0 + f.i02y);
+    const int brx = (int)(f.i00 * (double)R + f.i02x), bry = (int)(f.i00 * (double)R + f.i02y);
+    return FanWindow{ulx, uly, brx - ulx, bry - uly};
+}
+
+inline int check_fan_crop(const void* img, int H, int W, double x0, double y0, double x1, double y1, int R, int flip, int order,
+                          const void* out) {
+    const int rc = check_image("fan_crop", img, H, W);
+    if (rc != APF_OK) return rc;
+    if (!out) return fail(APF_ERR_INVALID, "fan_crop: null out");
+    if (R < 1 || R > APF_FAN_MAX_RES) return fail(APF_ERR_UNSUPPORTED, "fan_crop: R = %ld, served: 1..%ld", R, APF_FAN_MAX_RES);
+    if (flip != 0 && flip != 1) return fail(APF_ERR_INVALID, "fan_crop: flip = %ld", flip);
+    if (order != APF_FAN_RGB && order != APF_FAN_BGR) return fail(APF_ERR_INVALID, "fan_crop: channel order %ld", order);
+    if (!fan_box_ok(x0, y0, x1, y1)) return fail(APF_ERR_INVALID, "fan_crop: the box has no positive size inside +-%ld", 4L * APF_MAX_SIDE);
+    const FanWindow win = fan_window(x0, y0, x1, y1, R);
+    if (win.w < 1 || win.h < 1 || win.w > 4 * APF_MAX_SIDE || win.h > 4 * APF_MAX_SIDE)
+        return fail(APF_ERR_UNSUPPORTED, "fan_crop: window %ld x %ld, served: 1..%ld per axis", win.h, win.w, 4L * APF_MAX_SIDE);
+    return APF_OK;
+}
+
+inline int check_fan_decode(const void* hm, int B, int Hm, const double* boxes, const void* out) {
+    if (!hm || !boxes || !out) return fail(APF_ERR_INVALID, "fan_decode: null hm / boxes / out");
+    if (B < 1) return fail(APF_ERR_INVALID, "fan_decode: B = %ld", B);
+    if (Hm < 1) return fail(APF_ERR_INVALID, "fan_decode: Hm = %ld", Hm);
+    if (B > APF_FAN_MAX_B) return fail(APF_ERR_UNSUPPORTED, "fan_decode: B = %ld, served: 1..%ld", B, APF_FAN_MAX_B);
+    if (Hm > APF_FAN_MAX_RES) return fail(APF_ERR_UNSUPPORTED, "fan_decode: Hm = %ld, served: 1..%ld", Hm, APF_FAN_MAX_RES);
+    for (int b = 0; b < B; ++b)
+        if (!fan_box_ok(boxes[4 * b], boxes[4 * b + 1], boxes[4 * b + 2], boxes[4 * b + 3]))
+            return fail(APF_ERR_INVALID, "fan_decode: box %ld has no positive size inside +-%ld", b, 4L * APF_MAX_SIDE);
+    return APF_OK;
+}
+
 }  // namespace apf

@@ -14,7 +14,8 @@ JPEG on the GPU and muxed with the sound into ``<out>/output.avi`` here (util/av
 
 Landmark sources: ``--landmarks DIR`` (the reference's ``Alm_txt`` layout: ``ori.txt`` + ``%05d.txt``, 512-px coordinates
 for a 256-px photo -> ``--landmark_scale 0.5``), ``--landmarks_npy FILE`` ((T + 1, 68, 2): row 0 = the photo's), or the audio
-itself: ``--wav FILE --photo_landmarks TXT`` runs the audio half of main_end2end_module2.py:181-272 in process -- mel
+itself: ``--wav FILE --photo_landmarks TXT`` (or ``--photo_landmarks_from photo --fan_weights CKPT``, which detects them on the
+aligned picture on the device: landmarks.py) runs the audio half of main_end2end_module2.py:181-272 in process -- mel
 windows (audio.py) -> the two Module1 networks (``--load_a2l_G_name`` / ``--load_a2l_C_name`` checkpoints) -> the landmark
 post-processing -> image-pixel landmarks -- with the photo's detected (68, 3) landmarks (``face_alignment`` output, a txt of 68
 rows) and a speaker embedding as inputs: ``--speaker_emb`` txt of 256 numbers, or ``--speaker_emb_from wav --speaker_encoder
@@ -68,12 +69,38 @@ def load_matte(path, size):
     return torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0).view(1, 1, size, size)
 
 
+def aligned_photo_u8(a):
+    """the 512 x 512 aligned picture the photo's landmarks are detected on (main_end2end_module2.py:186-193 detects on the
+    picture align_mtcnn wrote): the result of --align mtcnn, or --photo itself, which must then be that picture"""
+    from PIL import Image
+    im = np.asarray(Image.open(a.photo).convert('RGB'))
+    if a.align == 'mtcnn':
+        from . import mtcnn
+        im = mtcnn.Detector(a.mtcnn_weights or mtcnn.DEFAULT_WEIGHTS).align_photo(im)
+        if im is None:
+            raise SystemExit('--align mtcnn: no face found in %s' % a.photo)
+    if im.shape[:2] != (512, 512):
+        raise SystemExit('--photo_landmarks_from photo with --align none: --photo is the aligned 512 x 512 picture, got %d x %d'
+                         % (im.shape[1], im.shape[0]))
+    return im
+
+
+def photo_landmarks_from_photo(a, device):
+    """the (68, 3) landmarks of the aligned picture, detected on the device (landmarks.py: FAN of --fan_weights)"""
+    from . import fan, landmarks
+    det = landmarks.PhotoLandmarks(fan.load_fan(a.fan_weights, device), device, mtcnn_weights=a.mtcnn_weights)
+    return det.detect(aligned_photo_u8(a), a.face_box).astype(np.float64)
+
+
 def landmarks_from_audio(a, device):
     """main_end2end_module2.py:205-272 in process (mel -> AutoVC conversion -> both Module1 networks -> post-processing), with
     the clip's f0 track and speaker embedding as inputs: returns (photo landmarks (68, 2), clip (T, 68, 2)) px.  With
     --module1_post device the clip is a CUDA tensor that never was on the host."""
     from . import audio, module1
-    shape = np.loadtxt(a.photo_landmarks).reshape(68, -1)
+    if getattr(a, 'photo_landmarks_from', None) == 'photo':
+        shape = photo_landmarks_from_photo(a, device)
+    else:
+        shape = np.loadtxt(a.photo_landmarks).reshape(68, -1)
     if shape.shape[1] == 2:
         shape = np.concatenate([shape, np.zeros((68, 1))], 1)
     std_z = np.loadtxt(a.std_face).reshape(68, 3)[:, 2] if a.std_face else None
@@ -131,6 +158,14 @@ def make_parser():
     ap.add_argument('--audio', default=None)
     ap.add_argument('--wav', default=None, help='drive the clip from this audio file (needs --photo_landmarks)')
     ap.add_argument('--photo_landmarks', default=None, help='txt, 68 rows "x y z": the photo\'s detected landmarks in pixels')
+    ap.add_argument('--photo_landmarks_from', choices=('txt', 'photo'), default='txt',
+                    help='where the photo\'s landmarks come from: txt = the file --photo_landmarks names, photo = detected on the '
+                         'aligned 512 x 512 picture on the GPU (landmarks.py: face_alignment\'s FAN restated, fed the --align mtcnn '
+                         'result, or --photo itself with --align none) with the checkpoint --fan_weights names')
+    ap.add_argument('--fan_weights', default=None, help="with --photo_landmarks_from photo: face_alignment's 3D-FAN checkpoint")
+    ap.add_argument('--face_box', type=_face_box, default=None,
+                    help='with --photo_landmarks_from photo: x0,y0,x1,y1 of the face in the aligned picture (default: the MTCNN '
+                         'detector\'s best face)')
     ap.add_argument('--speaker_emb', default=None, help='txt with the 256-d resemblyzer speaker embedding of the clip (required with --wav)')
     ap.add_argument('--speaker_emb_from', choices=('txt', 'wav'), default=None,
                     help='where the speaker embedding comes from: txt = the file --speaker_emb names, wav = computed from --wav on the '
@@ -193,6 +228,11 @@ def make_parser():
                     help='also write <out>/photo.png (the photo at --size) and <out>/ori_view.png (the photo with a red disc on each '
                          'of its landmarks), through --png_encoder')
     return ap
+
+
+def _face_box(text):
+    from .landmarks import parse_box
+    return parse_box(text)
 
 
 def _landmark_video_size(text):
@@ -314,8 +354,19 @@ def main(argv=None, prepare_model=None):
     a, rest = ap.parse_known_args(argv)
     if sum(x is not None for x in (a.landmarks, a.landmarks_npy, a.wav)) != 1:
         ap.error('exactly one of --landmarks / --landmarks_npy / --wav')
-    if a.wav is not None and a.photo_landmarks is None:
-        ap.error('--wav needs --photo_landmarks')
+    if a.photo_landmarks_from == 'photo':
+        if a.photo_landmarks is not None:
+            ap.error('--photo_landmarks_from photo detects the landmarks on the picture: it does not go with --photo_landmarks')
+        if a.wav is None:
+            ap.error('--photo_landmarks_from photo needs --wav')
+        if a.fan_weights is None:
+            ap.error('--photo_landmarks_from photo needs --fan_weights (face_alignment\'s 3D-FAN checkpoint)')
+    elif a.fan_weights is not None:
+        ap.error('--fan_weights goes with --photo_landmarks_from photo')
+    elif a.face_box is not None:
+        ap.error('--face_box goes with --photo_landmarks_from photo')
+    if a.wav is not None and a.photo_landmarks is None and a.photo_landmarks_from != 'photo':
+        ap.error('--wav needs --photo_landmarks (or --photo_landmarks_from photo)')
     if a.speaker_emb_from == 'wav':
         if a.speaker_emb is not None:
             ap.error('--speaker_emb_from wav computes the embedding from --wav: it does not go with --speaker_emb')

@@ -124,6 +124,39 @@ int32_t apf_crop_resize_cubic_ok(const uint8_t* img, int32_t H, int32_t W, int32
 int apf_crop_resize_cubic(const uint8_t* img, int32_t H, int32_t W, int32_t x0, int32_t y0, int32_t size, int32_t fill,
                           int32_t out_size, uint8_t* out, void* stream);
 
+/* ---- the photo's 68 landmarks: input and output side of the FAN network (fan.py; face_alignment's get_landmarks).
+ * A face box d = (x0, y0, x1, y1) fixes, in float64 and this operation order,
+ *     cx = x1 - (x1 - x0) / 2     cy = y1 - (y1 - y0) / 2 - (y1 - y0) * 0.12     scale = (x1 - x0 + y1 - y0) / 195
+ * and transform(p, S) = the inverse of [[a, 0, bx], [0, a, by], [0, 0, 1]] applied to (px, py, 1), with h = 200 scale, a = S / h,
+ * bx = S (0.5 - cx / h), by = S (0.5 - cy / h):  X = (1 / a) px + (-bx / a),  Y = (1 / a) py + (-by / a), nothing fused.
+ * Boxes are passed BY VALUE / from HOST memory: the arithmetic that decides a window's size runs in the launcher. */
+#define APF_FAN_POINTS 68
+#define APF_FAN_MAX_RES 1024    /* R of apf_fan_crop, Hm of apf_fan_decode */
+#define APF_FAN_MAX_B 16        /* images of one apf_fan_decode call */
+enum { APF_FAN_RGB = 0, APF_FAN_BGR = 1 };
+
+/* The network's input.  ul = trunc(transform((1, 1), R)), br = trunc(transform((R, R), R)); the (br.y - ul.y) x (br.x - ul.x)
+ * window holds image pixel (wy + ul.y, wx + ul.x) at (wy, wx) where that lies in the image and zero elsewhere; it is resized to
+ * R x R by OpenCV's 8-bit INTER_LINEAR rule (source index floor((d + 0.5) ratio - 0.5) with float weights rounded to 11 bits, a
+ * tap left of the window -> (0, weight 0), at or past its last pixel -> (last, weight 0); the vertical pass is
+ * (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2).  out (1 + flip, 3, R, R) fp32 = byte / 255; row 1 (flip == 1) is
+ * row 0 mirrored in x.  order APF_FAN_RGB: plane c is the image's channel c; APF_FAN_BGR: plane c is channel 2 - c.
+ * A window side outside 1 .. 4 * APF_MAX_SIDE is refused. */
+int32_t apf_fan_crop_ok(const uint8_t* img, int32_t H, int32_t W, double x0, double y0, double x1, double y1, int32_t R, int32_t flip,
+                        int32_t order, const float* out);
+int apf_fan_crop(const uint8_t* img, int32_t H, int32_t W, double x0, double y0, double x1, double y1, int32_t R, int32_t flip,
+                 int32_t order, float* out, void* stream);
+
+/* Heat maps -> landmarks.  hm (B, 68, Hm, Hm) fp32; hm_flipped: null, or the maps of the mirrored inputs, and the map that is read
+ * is then hm[b, j] + mirror_x(hm_flipped[b, pair[j]]) (fp32, in that order; pair: the 68-point mirror table).  Per (b, j): argmax
+ * (lowest flat index on ties), x = idx % Hm + 1, y = idx / Hm + 1; a peak strictly inside the map moves by a quarter pixel
+ * towards its larger neighbour on either axis (equal neighbours: not at all); minus 0.5; transform(., Hm) of box b in float64;
+ * truncate != 0 truncates toward zero; stored as fp32 in out (B, 68, 2).  boxes: B rows (x0, y0, x1, y1) in HOST memory, read
+ * before the call returns.  One workgroup per (b, j); the reduction's order is fixed. */
+int32_t apf_fan_decode_ok(const float* hm, const float* hm_flipped, int32_t B, int32_t Hm, const double* boxes, const float* out);
+int apf_fan_decode(const float* hm, const float* hm_flipped, int32_t B, int32_t Hm, const double* boxes, int32_t truncate, float* out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
