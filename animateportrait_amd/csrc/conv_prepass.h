@@ -388,7 +388,10 @@ __global__ __launch_bounds__(256) void norm_split_oct_kernel(const NormSplitPara
     float m4[4], r4[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { m4[i] = s_m[half * 4 + i]; r4[i] = s_r[half * 4 + i]; }
-    const float slope = p.act == 1 ? 0.f : (p.act == 2 ? 0.2f : 1.f);
+    // act(t) = max(t, slope * t), except that ReLU takes max(t, +0): 0.f * t is -0 for a negative t, and the head of a -0 is the
+    // bf16 0x8000 where norm_split_kernel (fmaxf(t, 0.f)) writes 0x0000 for the same value
+    const float slope = p.act == 2 ? 0.2f : 1.f;
+    const bool relu = p.act == 1;
     auto swap1 = [](unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false); };   // quad_perm [1,0,3,2]: the partner lane's value
 #pragma unroll
     for (int j = 0; j < VP; ++j) {
@@ -397,7 +400,7 @@ __global__ __launch_bounds__(256) void norm_split_oct_kernel(const NormSplitPara
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float t = (v[i] - m4[i]) * r4[i];
-            v[i] = fmaxf(t, slope * t);
+            v[i] = fmaxf(t, relu ? 0.f : slope * t);
         }
         if constexpr (RES == 2) {
             // even lane holds the 8 heads (dwords x, y = channels 0-3; z, w = 4-7), odd lane the 8 tails: each needs the head AND tail
@@ -460,7 +463,8 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const SplitRowsParams p
         m[c] = 0.f; rs[c] = 1.f;
         if (p.mean != nullptr) { m[c] = p.mean[n * CIN + c]; rs[c] = p.rstd[n * CIN + c]; }
     }
-    const float slope = p.act == 1 ? 0.f : (p.act == 2 ? 0.2f : 1.f);
+    const float slope = p.act == 2 ? 0.2f : 1.f;               // act(t) = max(t, slope * t); ReLU: max(t, +0) (0.f * t would be -0 for t < 0)
+    const bool relu = p.act == 1;
     bool okr[K];
 #pragma unroll
     for (int ky = 0; ky < K; ++ky) {
@@ -477,7 +481,7 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const SplitRowsParams p
 #pragma unroll
         for (int c = 0; c < CIN; ++c) {
             float t = (v[ky * CIN + c] - m[c]) * rs[c];
-            t = fmaxf(t, slope * t);
+            t = fmaxf(t, relu ? 0.f : slope * t);
             v[ky * CIN + c] = okr[ky] ? t : 0.f;
         }
 #pragma unroll
@@ -535,11 +539,12 @@ static __global__ __launch_bounds__(256) void split_s2d_kernel(const SplitS2dPar
     const float* const x0 = p.x + ((long long)n * p.C + g * 8) * HW + (ok ? sy * p.W + sx : 0);
 #pragma unroll
     for (int j = 0; j < 8; ++j) t[j] = x0[(long long)j * HW];
-    const float slope = p.act == 1 ? 0.f : (p.act == 2 ? 0.2f : 1.f);        // act(v) = max(v, slope * v)
+    const float slope = p.act == 2 ? 0.2f : 1.f;        // act(v) = max(v, slope * v); ReLU: max(v, +0) (0.f * v would be -0 for v < 0)
+    const bool relu = p.act == 1;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         float v = (t[j] - m[j]) * rs[j];
-        v = fmaxf(v, slope * v);
+        v = fmaxf(v, relu ? 0.f : slope * v);
         v = ok ? v : 0.f;
         __bf16 h, l;
         split_bf16(v, h, l);

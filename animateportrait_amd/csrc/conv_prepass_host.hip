@@ -93,6 +93,7 @@ int ap_split_prepass_rows(const ap_src* src, int32_t N, int32_t H, int32_t W, in
         return fail(AP_ERR_UNSUPPORTED, "split_prepass_rows: built for 7x7 stems with 1..4 input channels (K=%d, C=%d)", K, src->C);
     if (N < 1 || N > 65535 || H < 1 || W < 1) return fail(AP_ERR_INVALID, "split_prepass_rows: bad sizes");
     if ((src->mean == nullptr) != (src->rstd == nullptr)) return fail(AP_ERR_INVALID, "split_prepass_rows: mean/rstd mismatch");
+    if (src->act < 0 || src->act > 2) return fail(AP_ERR_INVALID, "split_prepass_rows: act %d", src->act);
     if (pad_mode == AP_PAD_REFLECT && pad >= H) return fail(AP_ERR_INVALID, "split_prepass_rows: reflection pad %d >= height", pad);
     SplitRowsParams p;
     memset(&p, 0, sizeof(p));

@@ -203,7 +203,9 @@ int ap_split_prepass(const ap_src* src, int32_t N, int32_t H, int32_t W, void* o
  * the split-bf16 path: the input is expanded to 32 "row channels" R[ky*C + c][y][x] = src[c][y + ky - pad][x]
  * (vertical padding applied here; `out`: ap_split_prepass_bytes(N, 32, H, W) bytes), and the stem becomes a 1 x 7
  * convolution over them: ap_conv2d_* with KH = 1, KW = 7, pad 3, one 32-channel source, presplit = 1 and weights
- * W'[co][ky*C + c][0][kx] = W[co][c][ky][kx] (zero for the unused channels).  One expansion serves all three stems. */
+ * W'[co][ky*C + c][0][kx] = W[co][c][ky][kx] (zero for the unused channels).  One expansion serves all three stems.
+ * src->act is AP_ACT_NONE, AP_ACT_RELU or AP_ACT_LRELU, as for ap_split_prepass and ap_split_prepass_s2d: any other value is
+ * AP_ERR_INVALID (it used to run as "no activation"). */
 int ap_split_prepass_rows(const ap_src* src, int32_t N, int32_t H, int32_t W, int32_t K, int32_t pad, int32_t pad_mode,
                           void* out, ap_stream_t stream);
 /* 4x4 stride-2 pad-1 layers (PatchGAN body, networks.py:2620-2636) on the split-bf16 path, as space-to-depth:
