@@ -41,6 +41,15 @@ struct SrcSeg {
     int pad_;
 };
 
+// which of up to kMaxSeg concatenated segments holds channel (or channel octet) c: begin1 / begin2 = where segments 1 and 2 start
+// (the weight-gradient operand passes and wgrad_xs.h; the convolutions look a chunk up in their own parameter block)
+__device__ __forceinline__ int concat_seg(int nseg, int c, int begin1, int begin2) {
+    int s = 0;
+    if (nseg > 1 && c >= begin1) s = 1;
+    if (nseg > 2 && c >= begin2) s = 2;
+    return s;
+}
+
 struct ConvKParams {
     SrcSeg seg[kMaxSeg];
     int nseg;

@@ -1,6 +1,6 @@
 // lds_dma.h -- what the matrix kernels share below the level of a kernel: the bf16 fragment type and the head / tail split, the
 // raw LDS-DMA issue, and the compile-time loop that gives every piece of a stage a constant index.
-// Users: conv_bf16x3.h (with conv_bf3_dma.h), conv_ph4.h, conv_tapgemm.h, wgrad_bf16x3.h, tools/variants/.
+// Users: conv_bf16x3.h (with conv_bf3_dma.h), conv_ph4.h, conv_tapgemm.h, wgrad_bf16x3.h, wgrad_xs.h, wgrad_operand.h, tools/variants/.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -33,6 +33,10 @@ template <int IMM>
 __device__ __forceinline__ void glds16_si(const void* sbase, unsigned voff, unsigned lds_base) {
     asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_base), "n"(IMM)
                  : "memory", "m0", "scc");
+}
+// LDS-DMA with a per-lane 64-bit source address (lane i lands at lds_addr + 16 i)
+__device__ __forceinline__ void glds16_vv(const void* src, unsigned lds_addr) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_addr) : "memory", "m0");
 }
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 

@@ -1,5 +1,5 @@
 // wgrad_plan.h -- the plan of one layer's weight gradient, shared by the planner (wgrad_plan.hip) and the launchers
-// (wgrad_launch.hip) of the general family (internal).  The edge layers (wgrad_edge_host.hip) have plans of their own.
+// (wgrad_launch.hip, wgrad_operand.hip) of the general family (internal).  The edge layers (wgrad_edge_host.hip) have plans of their own.
 //
 // The kernel tables take kernel addresses and so instantiate the kernels: they live in wgrad_launch.hip, and the planner reads
 // their entries (tile sizes, names) through the accessors below.  Only make_wgrad_plan writes a WgradPlan; the launchers read it.
@@ -103,5 +103,12 @@ bool split_transpose_whole_rows(int W, int s2d_c);
 int split_transpose_form(int nseg, bool any_b16, int C, int W, int pad, int X8, int Cp, int s2d_c, int rows_k);
 int split_transpose_refusal(int form);
 bool any_bf16_segment(const ap_src* segs, int nseg);
+// the operand passes of the bf16 GEMM (wgrad_operand.hip): an operand from fp32 / bf16 tensors, the shifted operand re-tiled from
+// the forward pass's split copies (C = channels of the view), and the shifted operand of a plan by whichever of the two serves it
+int launch_split_transpose(const ap_src* segs, int nseg, int N, int C, int H, int W, int pad, int pad_mode, int Hp, int X8, int Cp,
+                           uint4* out, hipStream_t stream, int s2d_c, int heads_only, int rows_k = 0);
+int launch_xs_transpose(const void* const* xs, const int* seg_c, int nseg, int N, int H, int W, int pad, int pad_mode, int Hp, int X8,
+                        int Cp, int parts, uint4* out, hipStream_t stream, int s2d_c = 0, int H0 = 0, int W0 = 0);
+int launch_bf16_gemm_operand(const ap_wgrad_desc* d, const WgradPlan& pl, bool from_xs, uint4* at, hipStream_t stream);
 
 }  // namespace apamd

@@ -20,7 +20,9 @@
 // 4-wave workgroup); the 2x2 space-to-depth forms of stride-2 layers, from the forward pass's space-to-depth copy or with the
 // view gathered from its plain copy (WgradXsParams::s2d_c).  Measurements and what was tried: profiles/r05_wgrad_routes.md.
 #pragma once
-#include "wgrad_bf16x3.h"
+#include "conv_igemm.h"     // kMaxSeg, concat_seg, reflect_clamp
+#include "lds_dma.h"
+#include "wgrad_bf3_partial.h"
 
 namespace apamd {
 
@@ -52,11 +54,6 @@ struct WgradXsCfg {
 };
 
 typedef short v4i16 __attribute__((ext_vector_type(4)));
-
-// LDS-DMA with a per-lane 64-bit source address (lane i lands at lds_addr + 16 i)
-__device__ __forceinline__ void glds16_vv(const void* src, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_addr) : "memory", "m0");
-}
 
 template <class C>
 __global__ __launch_bounds__(C::NT, C::WG_PER_CU) void wgrad_xs_kernel(const WgradXsParams p) {
@@ -114,9 +111,7 @@ __global__ __launch_bounds__(C::NT, C::WG_PER_CU) void wgrad_xs_kernel(const Wgr
                     code[i] |= r << 26;                              // the phase of this octet (bits 26-27)
                 }
             } else if (ao < p.a_cg_begin[p.nseg]) {
-                int sg = 0;
-                if (p.nseg > 1 && ao >= p.a_cg_begin[1]) sg = 1;
-                if (p.nseg > 2 && ao >= p.a_cg_begin[2]) sg = 2;
+                const int sg = concat_seg(p.nseg, ao, p.a_cg_begin[1], p.a_cg_begin[2]);
                 const int cgs = p.a_cg_begin[sg + 1] - p.a_cg_begin[sg];
                 obase[i] = (ao - p.a_cg_begin[sg]) * (HW + 1);
                 ostride[i] = cgs * (HW + 1);
@@ -249,13 +244,7 @@ __global__ __launch_bounds__(C::NT, C::WG_PER_CU) void wgrad_xs_kernel(const Wgr
         __syncthreads();
     }
 
-    const long long tile_floats = (long long)C::NWAVES * T * 1024;
-    float* out = p.partial + ((long long)split * p.m_tiles * p.c_tiles + (long long)mt * p.c_tiles + ct) * tile_floats +
-                 (long long)wave * T * 1024 + lane;
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[(t * 16 + r) * 64] = acc[t][r];
+    wgrad_bf3_store_partial<C::NWAVES, T>(p.partial, split, p.m_tiles, p.c_tiles, mt, ct, wave, lane, acc);
 }
 
 }  // namespace apamd

@@ -1,6 +1,6 @@
 """CPU: checks on the ISA of the built library (no GPU needed: llvm-objdump of the gfx950 code objects inside libapamd.so).
 
-The LDS-DMA primitive of the matrix kernels (csrc/lds_dma.h ``glds16_sv``: conv_bf16x3.h, wgrad_bf16x3.h, conv_ph4.h) writes M0 inside
+The LDS-DMA primitive of the matrix kernels (csrc/lds_dma.h ``glds16_sv`` / ``glds16_vv``: conv_bf16x3.h, wgrad_bf16x3.h, conv_ph4.h, wgrad_xs.h) writes M0 inside
 inline assembly and lists it as clobbered; hipcc warns that a clobber of a reserved register "may lead to undefined behaviour"
 because its register allocator does not model M0.  That is only a hazard if the COMPILER ever keeps a value of its own in M0
 across such a statement or emits an instruction that reads M0 implicitly.  This test makes the assumption a checked one: in

@@ -1,7 +1,7 @@
 """CPU (-m "not gpu"): the weight-gradient planner's answers, pinned.  tests/golden/wgrad_plans.json holds what every plan query of
 the backward half of the C ABI answered for a sweep of descriptors and shapes at commit 3f2dcd7 (the parent of the change that split
 make_wgrad_plan and wgrad_impl in what was then csrc/wgrad_host.hip into per-family steps and moved the edge-layer entry points to
-csrc/edge_host.hip; the planner is csrc/wgrad_plan.hip now, the launchers csrc/wgrad_launch.hip); this test replays the sweep and compares every field for equality.  The plan reads shapes and whether pointers
+csrc/edge_host.hip; the planner is csrc/wgrad_plan.hip now, the launchers csrc/wgrad_launch.hip and csrc/wgrad_operand.hip); this test replays the sweep and compares every field for equality.  The plan reads shapes and whether pointers
 are null, never memory, and without a GPU the planner assumes 256 compute units -- the MI355X's count -- so the table is the same on
 both kinds of machine.
 
