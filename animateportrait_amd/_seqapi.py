@@ -1,6 +1,6 @@
 """ctypes binding of libapseq.so (C ABI declared in include/animateportrait_seq.h): the batched LSTM forward of Module1's
-landmark networks, the clip-level post-processing of their landmark sequence, the clip's f0 track (f0.py) and the two ends of
-its speaker embedding (speaker.py).  Separate from _capi.py / libapamd.so, the boundary a model integrator binds.
+landmark networks, the clip-level post-processing of their landmark sequence, the clip's f0 track (f0.py), the two ends of
+its speaker embedding (speaker.py) and its audio front end (audio_device.py).  Separate from _capi.py / libapamd.so, the boundary a model integrator binds.
 Loaded on first use; as there, a missing library or a failed call raises -- there is no silent fallback."""
 import ctypes
 import os
@@ -20,8 +20,10 @@ SEG_CLOSE, SEG_LIP, SEG_NOSE = 1, 2, 4
 IMG_TRANSFORM, IMG_EYES = 1, 2
 F0_HOP, F0_CANDS, F0_STATES, F0_MIN_LAG, F0_MAX_LAG, F0_UNVOICED = 256, 19, 20, 2, 320, 255
 MEL_MIN_FFT, MEL_MAX_FFT, MEL_MAX_MELS, ALIGN_F64, SPK_E, SPK_MAX_B = 16, 1024, 128, 8, 256, 4096
+RS_MAX_RATE, RS_MAX_TAPS, RS_MAX_C, RS_MAX_L = 1024, 16384, 2, 0x3fffffff
+LOUD_MAX_N, LOUD_MAX_BLOCKS, FF_MAX_M, FF_MAX_L, FF_TILE = 8388607, 256, 8, 0x3fffffc0, 1024
 
-_i32, _ptr, _f32, _f64 = ctypes.c_int32, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
+_i32, _i64, _ptr, _f32, _f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
 # name -> (restype, argtypes); every symbol include/animateportrait_seq.h declares
 SIGNATURES = {
     'apq_abi_version': (_i32, []),
@@ -47,6 +49,19 @@ SIGNATURES = {
     'apq_mel_frames': (ctypes.c_int, [_ptr] * 4 + [_i32] * 5 + [_ptr]),
     'apq_speaker_head_ok': (_i32, [_ptr] * 5 + [_i32]),
     'apq_speaker_head': (ctypes.c_int, [_ptr] * 5 + [_i32] + [_ptr]),
+    # the clip's audio front end (audio_device.py)
+    'apq_resample_poly_ok': (_i32, [_ptr] * 3 + [_i32] * 5),
+    'apq_resample_poly': (ctypes.c_int, [_ptr] * 3 + [_i32] * 5 + [_ptr]),
+    'apq_loudness_workspace_bytes': (_i64, [_i32]),
+    'apq_loudness_sumsq_ok': (_i32, [_ptr] * 3 + [_i32]),
+    'apq_loudness_sumsq': (ctypes.c_int, [_ptr] * 3 + [_i32] + [_ptr]),
+    'apq_loudness_apply_ok': (_i32, [_ptr] * 2 + [_i32, _f64, _i32]),
+    'apq_loudness_apply': (ctypes.c_int, [_ptr] * 2 + [_i32, _f64, _i32] + [_ptr]),
+    'apq_filtfilt_workspace_bytes': (_i64, [_i32, _i32]),
+    'apq_filtfilt_ok': (_i32, [_ptr] * 6 + [_i32] * 2),
+    'apq_filtfilt': (ctypes.c_int, [_ptr] * 6 + [_i32] * 2 + [_ptr]),
+    'apq_logmel_frames_ok': (_i32, [_ptr] * 4 + [_i32] * 4),
+    'apq_logmel_frames': (ctypes.c_int, [_ptr] * 4 + [_i32] * 4 + [_ptr]),
 }
 
 _lib = None

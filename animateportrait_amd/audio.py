@@ -53,6 +53,12 @@ def resample_to_16k(x, sr):
     return signal.resample_poly(x, SAMPLE_RATE // g, int(sr) // g, axis=0)
 
 
+def loudness_gain(rms, target_dbfs=-20.0):
+    """The factor ``normalize_loudness`` applies to 16-bit samples of integer rms ``rms`` > 0 (audio_device.py computes its gain
+    with this very expression)."""
+    return 10.0 ** ((target_dbfs - 20.0 * np.log10(rms / 32768.0)) / 20.0)
+
+
 def normalize_loudness(x, target_dbfs=-20.0):
     """pydub ``sound.apply_gain(target_dBFS - sound.dBFS)`` on 16-bit samples: dBFS = 20 log10(rms / 32768) with the rms
     over ALL samples of all channels (audioop.rms), gain applied in the integer domain as audioop.mul does (clamp, then floor)."""
@@ -60,7 +66,7 @@ def normalize_loudness(x, target_dbfs=-20.0):
     rms = int(np.sqrt(np.mean(q.astype(np.float64) ** 2)))              # audioop.rms truncates to an integer
     if rms == 0:
         return q / 32768.0
-    gain = 10.0 ** ((target_dbfs - 20.0 * np.log10(rms / 32768.0)) / 20.0)
+    gain = loudness_gain(rms, target_dbfs)
     # audioop.mul (what AudioSegment.apply_gain runs): fbound() = clamp to [minval, maxval] -- anything below minval + 1 becomes
     # minval -- THEN floor toward -inf; not round-to-nearest
     v = q * gain
@@ -140,11 +146,18 @@ def window_frames(au, num_window_frames=WINDOW_FRAMES, step=1):
     return np.stack([au[i:i + num_window_frames] for i in range(0, n, step)])
 
 
-def clip_audio_features(path, max_frames=None, normalize=True, converter=None):
+def clip_audio_features(path, max_frames=None, normalize=True, converter=None, backend='host'):
     """wav file -> float32 windows (F, 18, 80) for ``module1.predict_landmarks*``; F output frames at 62.5 fps.
     converter: the AutoVC stage between the mel spectrogram and the windows (main_end2end_module2.py:218-224), a callable
     (T, 80) mel -> (T, 80) mel -- ``lambda mel: autovc.convert_mel(G, mel, f0, emb_src, emb_trg)``.  None hands the RAW mel to
-    the windows, which is NOT what checkpoints trained by the reference expect (they saw converted spectrograms)."""
+    the windows, which is NOT what checkpoints trained by the reference expect (they saw converted spectrograms).
+    backend: 'host' = numpy / scipy here; 'device' = audio_device.py (libapseq.so): a float32 CUDA tensor of windows, the converter
+    is called with the device mel; a clip the device does not serve is computed here after a printed notice."""
+    if backend == 'device':
+        from . import audio_device
+        return audio_device.clip_audio_features(path, max_frames, normalize, converter)
+    if backend != 'host':
+        raise ValueError("audio.clip_audio_features: backend %r (known: 'host', 'device')" % (backend,))
     x, sr = read_wav(path)
     x = resample_to_16k(x, sr)
     if normalize:

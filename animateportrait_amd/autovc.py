@@ -142,8 +142,11 @@ def _pad_seq(x, base=PAD_BASE):
 
 def convert_mel(G, mel, f0_norm, emb_src, emb_trg, device=None):
     """AutoVC_mel_Convertor_retrain_version.py:246-274: (T, 80) mel + (T,) normalised f0 (-1e10 / negative where unvoiced; None:
-    an all-unvoiced track) + the two 256-d speaker embeddings -> the converted (T, 80) mel ``x_identic_psnt``."""
+    an all-unvoiced track) + the two 256-d speaker embeddings -> the converted (T, 80) mel ``x_identic_psnt``.
+    A CUDA tensor ``mel`` (audio_device.ClipAudio.mel) stays on its device and the result is a CUDA tensor too."""
     device = device or next(G.parameters()).device
+    if torch.is_tensor(mel) and mel.is_cuda:
+        return _convert_mel_device(G, mel, f0_norm, emb_src, emb_trg)
     mel = np.asarray(mel)
     f0 = np.full(mel.shape[0], -1e10) if f0_norm is None else np.asarray(f0_norm)
     if f0.shape[0] != mel.shape[0]:
@@ -163,6 +166,32 @@ def convert_mel(G, mel, f0_norm, emb_src, emb_trg, device=None):
         from . import lstm_hip
         lstm_hip.check_timeouts()                            # (after the copy's synchronisation: a recurrence whose workgroups never met fails loudly)
     return res
+
+
+def _convert_mel_device(G, mel, f0_norm, emb_src, emb_trg):
+    """``convert_mel`` on a (T, 80) CUDA tensor: the same pieces and padding, nothing of the mel goes through the host"""
+    device = mel.device
+    T = mel.shape[0]
+    f0 = np.full(T, -1e10) if f0_norm is None else np.asarray(f0_norm.cpu() if torch.is_tensor(f0_norm) else f0_norm)
+    if f0.shape[0] != T:
+        raise ValueError('convert_mel: %d mel frames, %d f0 values' % (T, f0.shape[0]))
+    f0q = torch.from_numpy(quantize_f0_interp(f0)).to(device)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)[np.newaxis].astype('float32')).to(device)      # noqa: E731
+    e_src, e_trg = to(np.asarray(emb_src).reshape(-1)), to(np.asarray(emb_trg).reshape(-1))
+    mel = mel.to(torch.float32)
+    out, pad = [], 0
+    with torch.no_grad():
+        for i in range(0, T, PIECE):
+            n = min(PIECE, T - i)
+            pad = int(PAD_BASE * math.ceil(float(n) / PAD_BASE)) - n
+            x = nn.functional.pad(mel[i:i + n], (0, 0, 0, pad))[None]
+            f = nn.functional.pad(f0q[i:i + n], (0, 0, 0, pad))[None]
+            out.append(G(x, e_src, f, e_trg, f)[1])
+    y = torch.cat(out, 1)[0]
+    from . import lstm_hip
+    torch.cuda.current_stream(device).synchronize()
+    lstm_hip.check_timeouts()                                # (a recurrence whose workgroups never met fails loudly)
+    return y if pad == 0 else y[:-pad]
 
 
 def load_generator(path, device):

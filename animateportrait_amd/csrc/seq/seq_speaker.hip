@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "seq_dft.h"
 #include "seq_speaker_checks.h"
 
 namespace {
@@ -47,10 +48,7 @@ int launched(const char* what) {
     return APQ_OK;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
+__device__ __forceinline__ double wave_sum(double v) { return apq::dft_wave_sum(v); }
 
 // ------------------------------------------------------------------------------------------------------------------ mel frames
 struct MelParams {
@@ -68,42 +66,11 @@ __global__ __launch_bounds__(MT) void mel_frames_kernel(const MelParams p) {
     __shared__ double mag[apq::kMelBins];            // |X_k|^power
 
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int N = p.n_fft, nb = N / 2 + 1;
-    const long long first = (long long)t * p.hop - N / 2;     // the frame's first sample in the signal's own index
-
-    for (int n = tid; n < N; n += MT) {
-        // numpy's 'reflect'.  -N / 2 <= g <= L - 1 + N / 2 and L > N / 2: one reflection lands in [0, L)
-        long long g = first + n;
-        if (g < 0) g = -g;
-        if (g >= p.L) g = 2LL * (p.L - 1) - g;
-        fr[n] = (double)p.x[g] * p.window[n];
-        const double a = 2.0 * (double)n / (double)N;
-        tw[n] = make_double2(cospi(a), sinpi(a));
-    }
-    __syncthreads();
-
-    if (tid < nb) {
-        const int k = tid;                           // k <= N / 2 < N: one subtraction keeps idx = k n mod N below N
-        double re = 0.0, im = 0.0;
-        int idx = 0;
-        for (int n = 0; n < N; ++n) {
-            const double f = fr[n];
-            const double2 c = tw[idx];
-            re = fma(f, c.x, re);
-            im = fma(f, c.y, im);
-            idx += k;
-            idx = idx >= N ? idx - N : idx;
-        }
-        const double m2 = re * re + im * im;
-        mag[k] = p.power == 2 ? m2 : sqrt(m2);
-    }
-    __syncthreads();
+    const int nb = p.n_fft / 2 + 1;
+    apq::dft_frame_magnitudes<MT>(p.x, p.window, p.L, p.n_fft, p.hop, p.power, t, fr, tw, mag);      // (seq_dft.h)
 
     for (int m = wave; m < p.n_mels; m += MWAVES) {
-        const float* row = p.basis + (long long)m * nb;
-        double acc = 0.0;
-        for (int k = lane; k < nb; k += 64) acc = fma((double)row[k], mag[k], acc);
-        acc = wave_sum(acc);
+        const double acc = apq::mel_band_sum(p.basis + (long long)m * nb, mag, nb, lane);
         if (lane == 0) p.out[(long long)t * p.n_mels + m] = (float)acc;
     }
 }

@@ -117,6 +117,14 @@ def landmarks_from_audio(a, device):
         emb = speaker.speaker_embedding(x, sr, speaker.load_encoder(a.speaker_encoder, device))
     else:
         emb = np.loadtxt(a.speaker_emb).reshape(-1).astype(np.float32)
+    frontend = getattr(a, 'audio_frontend', None) or os.environ.get('APAMD_AUDIO_FRONTEND') or 'host'
+    if frontend not in ('host', 'device'):
+        raise ValueError("end2end: audio front end %r (known: 'host', 'device')" % (frontend,))
+    clip = None
+    if frontend == 'device':
+        # one read_wav, one upload; the mel, the f0 tracker and Module1's windows all start from this object (audio_device.py)
+        from . import audio_device
+        clip = audio_device.ClipAudio(a.wav, device=device)
     converter = None
     if not a.no_autovc:
         # main_end2end_module2.py:218-224: Module1 sees the AutoVC-converted spectrogram, not the raw mel
@@ -127,13 +135,19 @@ def landmarks_from_audio(a, device):
         if a.f0 == 'device':
             # the track of the samples clip_audio_features conditions: read, resample, loudness (f0.py conditions them itself)
             from . import f0 as f0_device
-            x, sr = audio.read_wav(a.wav)
-            f0 = f0_device.f0_track(audio.normalize_loudness(audio.resample_to_16k(x, sr)), a.f0_gender, device)
+            if clip is not None:
+                f0 = f0_device.f0_track(clip, a.f0_gender, device)
+            else:
+                x, sr = audio.read_wav(a.wav)
+                f0 = f0_device.f0_track(audio.normalize_loudness(audio.resample_to_16k(x, sr)), a.f0_gender, device)
         if f0 is None:
             print('WARNING: no --f0_npy: the converter runs on an all-unvoiced f0 track (the reference extracts RAPT f0 with '
                   'pysptk, which is not in this image)')
         converter = lambda mel: autovc.convert_mel(G, mel, None if f0 is None else f0[:mel.shape[0]], emb, emb_trg, device)   # noqa: E731
-    windows = audio.clip_audio_features(a.wav, max_frames=a.max_frames, converter=converter)
+    if clip is not None:
+        windows = audio_device.clip_audio_features(clip, max_frames=a.max_frames, converter=converter)
+    else:
+        windows = audio.clip_audio_features(a.wav, max_frames=a.max_frames, converter=converter)
     fl = module1.predict_landmarks_speaker_aware(net_g, net_c, windows, emb, face_id.reshape(-1))
     seq = module1.to_image_landmarks(fl, scale=scale, shift=shift)[:, :, :2]
     if torch.is_tensor(seq):
@@ -194,6 +208,10 @@ def make_parser():
                     help='where Module1\'s landmark post-processing runs (Savitzky-Golay filters, baseline calibration, lip fixes, '
                          'eye lids): host = numpy / scipy, device = libapseq.so, the landmark sequence then stays on the GPU; with '
                          '--triangulate device it never leaves it (default: host, or what APAMD_MODULE1_POST names)')
+    ap.add_argument('--audio_frontend', choices=('host', 'device'), default=None,
+                    help='where --wav is resampled, normalised, filtered and turned into mel windows: host = numpy / scipy '
+                         '(audio.py), device = libapseq.so (audio_device.py): the samples are uploaded once and the converter, '
+                         '--f0 device and Module1 read device tensors (default: host, or what APAMD_AUDIO_FRONTEND names)')
     ap.add_argument('--max_frames', type=int, default=None)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--size', type=int, default=256)

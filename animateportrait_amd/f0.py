@@ -98,11 +98,22 @@ def track(tab, gender='F', out=None):
 
 
 def f0_from_tracker_input(x, gender='F', device=None):
-    """``tracker_input`` -> f0_norm (T,) float64 numpy: both launches, then the one copy to the host (which synchronises)"""
+    """``tracker_input`` (numpy, a float32 CUDA tensor or an ``audio_device.ClipAudio``) -> f0_norm (T,) float64 numpy: both
+    launches, then the one copy to the host (which synchronises)"""
+    if hasattr(x, 'tracker_input'):
+        x = x.tracker_input()
+        if not x.is_cuda:                                    # a clip the device front end did not serve: its host signal
+            x = x.numpy()
     f0 = track(candidates(x, gender, device), gender)['f0'].cpu().numpy().astype(np.float64)
     return np.where(f0 < 0, UNVOICED, f0)
 
 
 def f0_track(samples_16k, gender='F', device=None):
-    """samples at 16 kHz (what ``audio.mel_spectrogram`` takes) -> f0_norm (T,) numpy, T the mel's frame count"""
+    """samples at 16 kHz (what ``audio.mel_spectrogram`` takes) -> f0_norm (T,) numpy, T the mel's frame count.
+    An ``audio_device.ClipAudio`` (or the CUDA tensor of its ``tracker_input()``) is tracked from its device signal: nothing is
+    conditioned on the host."""
+    if hasattr(samples_16k, 'tracker_input'):
+        return f0_from_tracker_input(samples_16k, gender, device)
+    if torch.is_tensor(samples_16k):
+        return f0_from_tracker_input(samples_16k, gender, device)
     return f0_from_tracker_input(tracker_input(samples_16k), gender, device)

@@ -14,7 +14,7 @@
  * enqueue on `stream` (a hipStream_t as void*), 0 = ok, negative = error with a thread-local message (apq_last_error()).
  * A refused call launches nothing and writes nothing; every launching call has a twin `<name>_ok` that needs no device.
  * The post-processing entry points were added without a change of APQ_ABI_VERSION: nothing that existed changed; so were the
- * clip's f0 track and the two ends of its speaker embedding (further down).
+ * clip's f0 track, the two ends of its speaker embedding and its audio front end (further down).
  */
 #ifndef ANIMATEPORTRAIT_SEQ_H
 #define ANIMATEPORTRAIT_SEQ_H
@@ -187,6 +187,67 @@ int apq_mel_frames(const float* x, const double* window, const float* basis, flo
  * embed is zero (the reference's arithmetic gives 0 / 0 in both places).  1 <= B <= APQ_SPK_MAX_B; 4-byte aligned pointers. */
 int32_t apq_speaker_head_ok(const float* h, const float* w, const float* b, const float* partial, const float* embed, int32_t B);
 int apq_speaker_head(const float* h, const float* w, const float* b, float* partial, float* embed, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------ the clip's audio front end (seq_audio.hip)
+ * What lies between the decoded samples and the mel windows (animateportrait_amd/audio.py: resample_to_16k,
+ * normalize_loudness, conditioned_signal, mel_spectrogram) on fp64 device tensors.  Each call is one launch, or two where the
+ * text says so, on the caller's stream; no atomics, no kernel waits for another workgroup; workspaces are the caller's.  The
+ * `_ok` twins and the error codes follow the rules of the post-processing calls above; fp64 tensors are 8-byte aligned
+ * (APQ_ALIGN_F64).  Added without a change of APQ_ABI_VERSION: nothing that existed changed. */
+#define APQ_RS_MAX_RATE 1024    /* up and down of apq_resample_poly, reduced by their common divisor by the caller */
+#define APQ_RS_MAX_TAPS 16384   /* taps of its filter (scipy designs 20 max(up, down) + 1: rates up to 819) */
+#define APQ_RS_MAX_C 2          /* channels */
+#define APQ_RS_MAX_L 0x3fffffff /* input samples per channel */
+#define APQ_LOUD_MAX_N 8388607  /* samples of all channels: N 2^30 < 2^53, so numpy's mean of the squares is exact too */
+#define APQ_LOUD_MAX_BLOCKS 256 /* partial sums of apq_loudness_sumsq */
+#define APQ_FF_MAX_M 8          /* order of apq_filtfilt's filter: b and a have M + 1 coefficients */
+#define APQ_FF_MAX_L 0x3fffffc0 /* samples */
+#define APQ_FF_TILE 1024        /* samples staged at a time */
+
+/* scipy.signal.resample_poly(x, up, down, axis=0) with the filter h the caller designed (scipy's default: a Kaiser-5.0 firwin
+ * of 20 max(up, down) + 1 taps, times up):
+ *   x [L][C] fp64, h [N] fp64, N odd  ->  y [ceil(L up / down)][C] fp64
+ * upfirdn's index arithmetic: the filter is delayed by down - (N / 2) % down zeros so that its centre falls on an output, the
+ * signal is zero outside [0, L), the first (N / 2 + that delay) / down outputs are dropped.  One thread per output sample; the
+ * taps of that sample's phase only, added in ascending tap order in fp64 (fused multiply-add). */
+int32_t apq_resample_poly_ok(const double* x, const double* h, const double* y, int32_t L, int32_t C, int32_t N, int32_t up,
+                             int32_t down);
+int apq_resample_poly(const double* x, const double* h, double* y, int32_t L, int32_t C, int32_t N, int32_t up, int32_t down,
+                      void* stream);
+
+/* pydub's apply_gain on 16-bit samples in two halves (audio.normalize_loudness); x [N] fp64, all channels alike.
+ * apq_loudness_sumsq: q = clip(rint(32768 x), -32768, 32767) (round half to even), *sum = the exact 64-bit integer sum of q^2.
+ *   Two launches: partial sums of up to APQ_LOUD_MAX_BLOCKS workgroups into workspace (apq_loudness_workspace_bytes(N) bytes),
+ *   then one workgroup adds them.  The caller reads the 8 bytes back and computes the gain.
+ * apq_loudness_apply: y = floor(v) / 32768 with v = q gain, v > 32767 -> 32767, v < -32767 -> -32768 (audioop's fbound, then
+ *   floor); with apply_gain == 0 (an rms of 0) y = q / 32768 and gain is ignored.  y may be x. */
+int64_t apq_loudness_workspace_bytes(int32_t N);
+int32_t apq_loudness_sumsq_ok(const double* x, const void* workspace, const int64_t* sum, int32_t N);
+int apq_loudness_sumsq(const double* x, void* workspace, int64_t* sum, int32_t N, void* stream);
+int32_t apq_loudness_apply_ok(const double* x, const double* y, int32_t N, double gain, int32_t apply_gain);
+int apq_loudness_apply(const double* x, double* y, int32_t N, double gain, int32_t apply_gain, void* stream);
+
+/* scipy.signal.filtfilt(b, a, x) with its defaults, one channel, fp64, out of place: x [L] -> y [L].  b, a [M + 1] and
+ * zi [M] = lfilter_zi(b, a) are HOST arrays (they travel in the launch's arguments); 1 <= M <= APQ_FF_MAX_M, L > 3 (M + 1).
+ * The signal is extended oddly by 3 (M + 1) samples at both ends, filtered forward from zi ext[0], the result filtered
+ * backward from zi (its last sample), the extension dropped.  Every sample is lfilter's transposed direct form II step with
+ * lfilter's own operation order and no fused multiply-add, one sample after the other, so the result has scipy's bits: the
+ * recurrence is NOT evaluated in parallel (DESIGN.md 4e-4 says why a blocked scan cannot be).  One launch of one workgroup:
+ * its lanes stage tiles of APQ_FF_TILE samples between memory and LDS while one lane runs the recurrence.
+ * workspace: apq_filtfilt_workspace_bytes(L, M) bytes (the forward pass's output). */
+int64_t apq_filtfilt_workspace_bytes(int32_t L, int32_t M);
+int32_t apq_filtfilt_ok(const double* x, const double* y, const double* b, const double* a, const double* zi, const void* workspace,
+                        int32_t L, int32_t M);
+int apq_filtfilt(const double* x, double* y, const double* b, const double* a, const double* zi, void* workspace, int32_t L,
+                 int32_t M, void* stream);
+
+/* apq_mel_frames on fp64 samples with the reference's output map (audio.mel_spectrogram):
+ *   out [T][n_mels] fp32 = (20 log10(max(1e-5, |STFT| basis)) - 16 + 100) / 100,   T = L / hop + 1
+ * carried in fp64 and rounded to fp32 once, at the store.  Served as apq_mel_frames (power 1), x 8-byte aligned. */
+int32_t apq_logmel_frames_ok(const double* x, const double* window, const float* basis, const float* out, int32_t L, int32_t n_fft,
+                             int32_t hop, int32_t n_mels);
+int apq_logmel_frames(const double* x, const double* window, const float* basis, float* out, int32_t L, int32_t n_fft, int32_t hop,
+                      int32_t n_mels, void* stream);
 
 #ifdef __cplusplus
 }
