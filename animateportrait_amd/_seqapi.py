@@ -30,6 +30,11 @@ SIGNATURES = {
     'apq_last_error': (ctypes.c_char_p, []),
     'apq_lstm_layer_fwd_ok': (_i32, [_ptr] * 6 + [_i32] * 5),
     'apq_lstm_layer_fwd': (ctypes.c_int, [_ptr] * 6 + [_i32] * 5 + [_ptr]),
+    # the training pair of that layer (lstm_hip.lstm_train_batched)
+    'apq_lstm_layer_fwd_train_ok': (_i32, [_ptr] * 8 + [_i32] * 4),
+    'apq_lstm_layer_fwd_train': (ctypes.c_int, [_ptr] * 8 + [_i32] * 4 + [_ptr]),
+    'apq_lstm_layer_bwd_ok': (_i32, [_ptr] * 5 + [_i32] * 4),
+    'apq_lstm_layer_bwd': (ctypes.c_int, [_ptr] * 5 + [_i32] * 4 + [_ptr]),
     # clip-level landmark post-processing (landmark_post.py); each launching call = its _ok twin + the stream
     'apq_savgol_ok': (_i32, [_ptr] * 4 + [_i32] * 7),
     'apq_savgol': (ctypes.c_int, [_ptr] * 4 + [_i32] * 7 + [_ptr]),

@@ -16,7 +16,8 @@ APAMD_MODULE1_LSTM=hip) moves their LSTMs to the batched kernel of libapseq.so. 
 235-245, 247-309, 594-617) followed by the clip-level post-processing of main_end2end_module2.py:262-272; the simpler
 ``predict_landmarks`` is the content branch alone (``__train_face_wo_pos__``).  That post-processing is numpy / scipy on the host
 by default; ``set_post_backend('device')`` (or APAMD_MODULE1_POST=device) runs it in libapseq.so (landmark_post.py) and keeps the
-landmark sequence on the GPU.  NOT built: the AutoVC mel / speaker
+landmark sequence on the GPU.  Training the content branch is module1_train.py; ``set_lstm_train_backend('hip')`` (or
+APAMD_MODULE1_LSTM_TRAIN=hip) puts its LSTM on the training kernel pair of libapseq.so.  NOT built: the AutoVC mel / speaker
 embedding front end (librosa / pysptk / pyworld / resemblyzer are not in this image, and neither are the checkpoints);
 callers pass the (T, 18, 80) mel windows and the 256-d speaker embedding the reference's ``au_data`` / ``au_emb`` hold.
 """
@@ -84,8 +85,31 @@ def get_post_backend():
     return _post_backend
 
 
-def _lstm_last(lstm, x):
-    """``lstm(x)[0][:, -1, :]``, the one thing both networks read from their LSTM"""
+# Who runs the content branch's LSTM when it is TRAINED (module in training mode, gradients enabled): 'library' = nn.LSTM,
+# 'hip' = one apq_lstm_layer_fwd_train / apq_lstm_layer_bwd launch pair per layer (lstm_hip.lstm_train_batched).  Separate from
+# the inference switch above, which it leaves alone.
+_lstm_train_backend = _checked_backend(os.environ.get('APAMD_MODULE1_LSTM_TRAIN') or 'library')
+
+
+def set_lstm_train_backend(name):
+    """Select the LSTM backend of ``Audio2LandmarkContent`` in training; returns the previous one."""
+    global _lstm_train_backend
+    prev, _lstm_train_backend = _lstm_train_backend, _checked_backend(name)
+    return prev
+
+
+def get_lstm_train_backend():
+    return _lstm_train_backend
+
+
+def _lstm_last(lstm, x, trainable=False):
+    """``lstm(x)[0][:, -1, :]``, the one thing both networks read from their LSTM.  ``trainable``: the caller takes part in the
+    training switch (the content branch)."""
+    if trainable and lstm.training and torch.is_grad_enabled():
+        if _lstm_train_backend == 'hip':
+            from . import lstm_hip
+            return lstm_hip.lstm_train_batched(lstm, x, last_only=True)
+        return lstm(x)[0][:, -1, :]
     if _lstm_backend == 'hip':
         from . import lstm_hip
         return lstm_hip.lstm_forward_batched(lstm, x, last_only=True)
@@ -116,7 +140,7 @@ class Audio2LandmarkContent(nn.Module):
         x = au
         if self.use_prior_net:
             x = self.fc_prior(x.contiguous().view(-1, self.in_size)).view(-1, self.num_window_frames, self.lstm_size)
-        output = _lstm_last(self.bilstm, x)
+        output = _lstm_last(self.bilstm, x, trainable=True)
         if face_id.shape[0] == 1:
             face_id = face_id.repeat(output.shape[0], 1)
         return self.fc(torch.cat((output, face_id), dim=1)), face_id
@@ -473,8 +497,20 @@ def load_module1(speaker_ckpt, content_ckpt, device=None):
     sd = net_g.state_dict()
     sd.update({k: v for k, v in ck['G'].items() if k.split('.')[0] not in ['comb_mlp']})   # :64-66
     net_g.load_state_dict(sd)
-    net_c = Audio2LandmarkContent(use_prior_net=True, drop_out=0.5)                  # :71-73
-    net_c.load_state_dict(torch.load(content_ckpt, map_location='cpu')['model_g_face_id'])   # :76-77
+    sd_c = torch.load(content_ckpt, map_location='cpu')['model_g_face_id']
+    # :71-73 builds it with the prior net; a checkpoint of module1_train.py trained without one says so by its LSTM's width
+    # (161 against the 80 mel bands).  A network whose lstm_size equals its in_size cannot be told apart this way: such a
+    # checkpoint is not the reference's and is not served here
+    for key in ('bilstm.weight_ih_l0', 'fc_prior.0.weight'):
+        if key not in sd_c:
+            raise KeyError('load_module1: %s has no %r under model_g_face_id: not a content-branch checkpoint' % (content_ckpt, key))
+    width, in_size = sd_c['bilstm.weight_ih_l0'].shape[1], sd_c['fc_prior.0.weight'].shape[1]
+    if width not in (in_size, 161):
+        raise ValueError('load_module1: %s has an LSTM input width of %d: served are %d (no prior net) and 161 (prior net)'
+                         % (content_ckpt, width, in_size))
+    prior = width != in_size
+    net_c = Audio2LandmarkContent(use_prior_net=prior, drop_out=0.5)
+    net_c.load_state_dict(sd_c)                                                      # :76-77
     for n in (net_g, net_c):
         n.eval()
         for q in n.parameters():

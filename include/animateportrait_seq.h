@@ -1,7 +1,8 @@
 /*
  * animateportrait_seq.h -- C ABI of libapseq.so: the batched LSTM forward of Module1's two landmark networks
  * (Module1/src/models/model_audio2landmark.py:41-55 and :312-318: 3-layer LSTMs with 256 hidden units over up to 512
- * windows of 18 frames) on the MI355X (gfx950), and the clip-level post-processing of their landmark sequence
+ * windows of 18 frames) on the MI355X (gfx950), the training pair of that layer (a forward that keeps its gates, and the
+ * reverse-time recurrence: Module1/src/approaches/train_content.py), and the clip-level post-processing of their landmark sequence
  * (train_audio2landmark.py:101-141, 235-309, 594-617 and main_end2end_module2.py:262-272): Savitzky-Golay smoothing,
  * baseline calibration, segment assembly with the inverted-lip fix, the image transform with the eye lids.
  *
@@ -57,6 +58,37 @@ int32_t apq_lstm_layer_fwd_ok(const float* x, const float* w_ih, const float* w_
                               const float* out, int32_t B, int32_t T, int32_t I, int32_t H, int32_t last_only);
 int apq_lstm_layer_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* out,
                        int32_t B, int32_t T, int32_t I, int32_t H, int32_t last_only, void* stream);
+
+/* ------------------------------------------------------------- training the same layer (seq_lstm_train.hip)
+ * One launch each, a workgroup per 16 batch rows as above: no atomics, no workspace, no traffic between workgroups.  Served:
+ * H = 256 and the APQ_MAX_* limits of apq_lstm_layer_fwd; gates / dgates of B T 4H elements below 2^31; x, w_ih and the biases
+ * aligned as there, every other tensor to 16 bytes (APQ_ALIGN_WIDE).  The `_ok` twins and the error codes follow the rules of
+ * apq_lstm_layer_fwd_ok.  Added without a change of APQ_ABI_VERSION: nothing that existed changed.
+ *
+ * apq_lstm_layer_fwd_train: apq_lstm_layer_fwd with last_only = 0 that also writes, per step, the activated gates
+ *   gates [B][T][4H]  (i, f, g, o: sigmoid, sigmoid, tanh, sigmoid of the four H-wide blocks)  and  cell [B][T][H] = c_t.
+ * `out` has the bits apq_lstm_layer_fwd writes: the same products in the same order, the same gate functions. */
+int32_t apq_lstm_layer_fwd_train_ok(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                                    const float* out, const float* gates, const float* cell, int32_t B, int32_t T, int32_t I,
+                                    int32_t H);
+int apq_lstm_layer_fwd_train(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* out,
+                             float* gates, float* cell, int32_t B, int32_t T, int32_t I, int32_t H, void* stream);
+
+/* The reverse-time recurrence of that layer: from the gradient of its output to the gradient of its pre-activation gates,
+ *   dout    [B][T][H], or with last_only != 0 [B][H]: the gradient of h_{T-1}, every other step's being zero
+ *   gates, cell       what apq_lstm_layer_fwd_train wrote
+ *   w_hh_t  [H][4H]   the transpose of w_hh, made by the caller
+ *   dgates  [B][T][4H]  dG_t, gate order i, f, g, o
+ * per step, t = T - 1 .. 0, with dh_rec = dc_carry = 0 at the start and c_{-1} = 0:
+ *   dh = dout_t + dh_rec,  do = dh tanh(c_t) o (1 - o),  dc = dh o (1 - tanh^2 c_t) + dc_carry,  di = dc g i (1 - i),
+ *   df = dc c_{t-1} f (1 - f),  dg = dc i (1 - g^2),  dc_carry = dc f,  dh_rec = dG_t w_hh
+ * (dh_rec: one product over K = 4H per step on the fp32 matrix pipe, the 16 x 4H tile of dG_t staged in LDS.)  The
+ * time-parallel products are the caller's GEMMs over the B T rows of dgates: dx = dG w_ih, dw_ih = dG^T x, dw_hh = dG^T h_{t-1},
+ * db_ih = db_hh = the column sums.  The order of every sum is the same for every row and launch. */
+int32_t apq_lstm_layer_bwd_ok(const float* dout, const float* gates, const float* cell, const float* w_hh_t, const float* dgates,
+                              int32_t B, int32_t T, int32_t H, int32_t last_only);
+int apq_lstm_layer_bwd(const float* dout, const float* gates, const float* cell, const float* w_hh_t, float* dgates, int32_t B,
+                       int32_t T, int32_t H, int32_t last_only, void* stream);
 
 /* ---------------------------------------------------------------- clip-level landmark post-processing (seq_post.hip)
  * A landmark sequence is [T][204] fp32: 68 points x (x, y, z) per frame.  No call uses atomics, a workspace or a host
