@@ -1,5 +1,7 @@
-// The draw2 rasteriser of apd_landmark_map as per-pixel predicates (host and device: a stand-alone host program runs the
-// same functions under sanitizers, tools/raster_host_check.cpp).
+// OpenCV's integer line / circle drawing rules as per-pixel predicates, the project's one statement of them: the draw2
+// rasterisers apd_landmark_map and apd_landmark_vis (libapdata) and ap_lip_line_mask, ap_landmark_discs and ap_circle_rows
+// (libapamd, landmark_masks.hip) all test pixels through these functions (host and device: a stand-alone host program runs
+// the same functions under sanitizers, tools/raster_host_check.cpp).
 //
 // OpenCV 4.2 draws cv2.line(thickness) incrementally: ThickLine -> the quad p +- dp through FillConvexPoly at 16.16 fixed
 // point (its outline by Line2, its interior by scanlines whose edge positions advance by a rounded slope per row) plus a
@@ -45,6 +47,12 @@ inline CircleRows circle_rows(int r) {
 // np.round(v).astype(int): ties to even.  NaN and values beyond +-COORD_MAX land on the clamp.
 APD_HD int round_coord(float v) {
     const float r = rintf(v);
+    return (int)fminf(fmaxf(r, (float)-COORD_MAX), (float)COORD_MAX);
+}
+
+// int(v) of the Python binding (getlipline): truncation toward zero, then the same clamp
+APD_HD int trunc_coord(float v) {
+    const float r = truncf(v);
     return (int)fminf(fmaxf(r, (float)-COORD_MAX), (float)COORD_MAX);
 }
 

@@ -2,7 +2,7 @@
 // (include/animateportrait_data.h).
 //
 // landmark_map: one workgroup per (sample, TH rows).  The rounded points and, for op 1, the integer description of every
-// contour segment that can touch those rows (landmark_raster.h) are built once in LDS, one lane per segment; then every
+// contour segment that can touch those rows (cv_raster.h) are built once in LDS, one lane per segment; then every
 // lane tests its pixels against them and stores hi or lo -- consecutive lanes write consecutive columns, every element of
 // the output is written exactly once, and nothing is accumulated in memory, so there is neither a memset nor an atomic.
 #include <hip/hip_runtime.h>
@@ -11,7 +11,7 @@
 
 #include "../../../include/animateportrait_data.h"
 #include "apd_common.h"
-#include "landmark_raster.h"
+#include "../cv_raster.h"
 
 namespace {
 

@@ -3,9 +3,9 @@
 // A frame is drawn in painter's order -- the background, then the segments 0 .. S-1 as cv2.line, then the P filled discs --
 // and a later primitive overwrites an earlier one.  Read backwards that is a search: the colour of a pixel is the colour of
 // the LAST primitive that covers it, so the discs are tried first, then the segments from S-1 down to 0, and the first hit
-// ends the scan.  The coverage tests are the predicates of landmark_raster.h, unchanged.
+// ends the scan.  The coverage tests are the predicates of cv_raster.h, unchanged.
 #pragma once
-#include "landmark_raster.h"
+#include "../cv_raster.h"
 
 namespace apd_raster {
 

@@ -2,7 +2,7 @@
 // (main_end2end_module2.py:47-68) and of the marked photo it leaves beside it (include/animateportrait_data.h).
 //
 // The shape of landmark_map_kernel: one workgroup per (frame, TH rows).  The clamped points, the integer description of
-// every segment that can touch those rows (landmark_raster.h; a segment that misses them gets an empty box) and the
+// every segment that can touch those rows (cv_raster.h; a segment that misses them gets an empty box) and the
 // segments' colours as frame values are built once in LDS, one lane per segment.  Then every lane finds the primitive on
 // top of its pixels by the backward scan of landmark_vis.h and stores the three planes: consecutive lanes write
 // consecutive columns -- four columns per lane as one 16-byte store when the rows allow it -- every element of the output

@@ -577,14 +577,17 @@ int ap_pixel_shuffle2(const float* x, int32_t N, int32_t C, int32_t H, int32_t W
 /* getlipline (Module2/models/geomgm_ifw_fore_model.py:507-515): out[n] (size x size, {0, 1}) = union over the segments
  * (seg_a[i], seg_b[i]) of cv2.line(mask, lands[n][a], lands[n][b], 255, thickness) -- OpenCV 4.2 ThickLine (quad through
  * FillConvexPoly at 16.16 fixed point + a filled circle at both ends), float coordinates truncated to int as the Python
- * binding does.  lands: device (N, P, 2) as (x, y); seg_a / seg_b: HOST arrays of nseg <= 32 landmark indices;
- * thickness 2..16.  replaces the numpy + cv2 loop of getlipline (one launch + one memset). */
+ * binding does (then clamped to +-2^20; NaN lands on the clamp).  lands: device (N, P, 2) as (x, y); seg_a / seg_b: HOST
+ * arrays of nseg <= 32 landmark indices; thickness 2..16; N <= 65535.  The rule is csrc/cv_raster.h's per-pixel predicates,
+ * the ones apd_landmark_map uses: one launch stores every element of out exactly once (out needs no initial value), and
+ * its work is proportional to N * size^2 whatever the coordinates are.  Replaces the numpy + cv2 loop of getlipline. */
 int ap_lip_line_mask(const float* lands, int32_t N, int32_t P, const int32_t* seg_a, const int32_t* seg_b, int32_t nseg,
                      int32_t size, int32_t thickness, float* out, ap_stream_t stream);
 /* draw2(op=0) (Module2/data/umlvdfw_test_dataset.py:34-41): filled cv2.circle(radius) at np.round(lm) for every
  * landmark; out N x 1 x H x W = hi inside / lo outside (the reference: +1 / -1).  The disc is OpenCV's octant-walk
- * fill (drawing.cpp Circle(), opencv-python 4.2 pinned by requirements.txt:2), whose row half-widths
- * ap_circle_rows returns (hw[0..radius]); radius <= 31. */
+ * fill (drawing.cpp Circle(), opencv-python 4.2 pinned by requirements.txt:2) as csrc/cv_raster.h states it
+ * (circle_rows / circle_covers, shared with apd_landmark_map); rounded coordinates are clamped to +-2^20, NaN lands on
+ * the clamp.  ap_circle_rows returns that header's row half-widths on the host (hw[0..radius]); radius <= 31. */
 int ap_landmark_discs(const float* lm, int32_t N, int32_t P, int32_t H, int32_t W, int32_t radius, float lo, float hi,
                       float* out, ap_stream_t stream);
 int ap_circle_rows(int32_t radius, int32_t* hw);

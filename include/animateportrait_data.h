@@ -81,7 +81,8 @@ int apd_image_prep_u8(const apd_image_prep* d, const uint8_t* src, const int32_t
  *   seg_host  the same table on the host: every index is checked against P here, before the launch.  The kernel clamps
  *             what it reads from `seg` into [0, P), so a device table that differs gives wrong pixels, never a wild access.
  *   out       device (N, 1, H, W) float32, every element written: `hi` on a mark, `lo` elsewhere (no memset needed)
- * op 0: the union of filled cv2.circle(radius) discs -- bit-equal to ap_landmark_discs.
+ * op 0: the union of filled cv2.circle(radius) discs -- bit-equal to ap_landmark_discs, which tests pixels through the same
+ *       header (csrc/cv_raster.h: round_coord, circle_rows, circle_covers).
  * op 1: the discs, then the union of cv2.line(start, end, color, thickness) over the segments by OpenCV 4.2's ThickLine
  *       rule as oracle/cv_raster.thick_line restates it: the quad through FillConvexPoly at 16.16 fixed point plus a filled
  *       circle of radius (thickness + 1) >> 1 at both ends.  thickness 1 follows the same quad rule (cv2 itself draws a

@@ -1,5 +1,5 @@
-"""GPU (-m gpu): the loss-side kernels of csrc/losses.hip at three channels and at their contract edges -- compositing with
-a C-channel background and an appended mask channel, crop + resize on H != W frames with overhanging / short / oversized /
+"""GPU (-m gpu): the loss-side kernels of csrc/losses.hip and csrc/landmark_masks.hip at three channels and at their
+contract edges -- compositing with a C-channel background and an appended mask channel, crop + resize on H != W frames with overhanging / short / oversized /
 one-pixel windows and the three-channel maps, the rasterisers and flow_post off their one production shape, the L1
 backward's zero branch, ap_axpy, the C-side refusals, and sentinel-padded outputs behind every kernel.
 
@@ -413,6 +413,94 @@ def test_lip_line_mask_refusals(dev):
         assert lib.ap_lip_line_mask(ptr(lands), 2, 20, a, b, len(segs), 33, th, ptr(out), stream()) == AP_ERR_INVALID
         torch.cuda.synchronize()
         assert bool((buf == SENTINEL).all()), (th, segs)
+
+
+def _lip_oracle(size, lands, segs, thickness):
+    from oracle import cv_raster as cr
+    return np.stack([cr.lip_line_mask(size, l.double().numpy(), segs, thickness) for l in lands])
+
+
+@pytest.mark.parametrize('nseg', [1, 32])
+@pytest.mark.parametrize('thickness', [2, 16])
+@pytest.mark.parametrize('size', [1, 16, 17])
+def test_lip_line_mask_row_tile_edges(dev, size, thickness, nseg):
+    """The kernel works on tiles of 16 rows: size 1 (one short tile), 16 (one full tile) and 17 (a full tile and a tile of a
+    single row), with one segment and with 32, the limit.  Segment 0 runs from above the canvas to below it, so it crosses
+    the tile boundary; the others are a random chain on and off the frame.  Bit-equal to oracle/cv_raster.py."""
+    from animateportrait_amd import losses
+    g = torch.Generator().manual_seed(1000 * size + 10 * thickness + nseg)
+    lands = torch.rand(3, nseg + 1, 2, generator=g) * (size * 1.6) - size * 0.3
+    lands[:, 0] = torch.tensor([0.2 * size, -2.5])
+    lands[:, 1] = torch.tensor([0.8 * size, size + 1.5])
+    lands[1, :2] = lands[1, :2].flip(1)                            # sample 1: the same crossing, x-major
+    segs = [(i, i + 1) for i in range(nseg)]
+    got = losses.lip_line_mask(lands.to(dev), segs, size, thickness).cpu()
+    assert got.shape == (3, 1, size, size)
+    want = _lip_oracle(size, lands, segs, thickness)
+    assert np.array_equal(got[:, 0].numpy(), want), (size, thickness, nseg, float(np.abs(got[:, 0].numpy() - want).sum()))
+    assert want[0, -1].sum() > 0 and want[0, 0].sum() > 0           # the crossing segment marks the first and the last row
+
+
+def test_lip_line_mask_writes_every_element(dev):
+    """The raw entry point into a buffer pre-filled with NaN (no memset precedes the kernel, which stores every element
+    itself): bit-equal to the oracle, hence without a NaN, and nothing behind the output is touched."""
+    from animateportrait_amd.models.geomgm_ifw_fore_model import LIP_SEGMENTS
+    lib, ptr, stream = _api()
+    size, n, th = 33, 2, 3
+    lands = _lip_lands(size, torch.Generator().manual_seed(330))[:n]
+    k = len(LIP_SEGMENTS)
+    a = (ctypes.c_int32 * k)(*[s[0] for s in LIP_SEGMENTS])
+    b = (ctypes.c_int32 * k)(*[s[1] for s in LIP_SEGMENTS])
+    buf = torch.full((n * size * size + PAD,), float('nan'), device=dev)
+    assert lib.ap_lip_line_mask(ptr(lands.to(dev)), n, 68, a, b, k, size, th, ptr(buf), stream()) == 0
+    torch.cuda.synchronize()
+    got = buf[:n * size * size].view(n, size, size).cpu()
+    assert not bool(torch.isnan(got).any()) and bool(torch.isnan(buf[n * size * size:]).all())
+    assert np.array_equal(got.numpy(), _lip_oracle(size, lands, LIP_SEGMENTS, th))
+    assert float(got[0].sum()) > 0 and float((got == 0).sum()) > 0
+
+
+@pytest.mark.parametrize('thickness', [2, 16])
+def test_lip_line_mask_bounded_work_and_clamping(dev, thickness):
+    """Size 33, three samples of a 20-segment ring plus one more segment.  Samples 0 and 2: the ring on and off the frame and
+    a segment from -4096 to +4096 that crosses the canvas -- bit-equal to the oracle.  Sample 1: every end point at +-2^21 to
+    the left of the canvas and one point NaN (which the coordinate clamp sends to the same side) -- all zero: a segment
+    whose clamped box misses the canvas costs nothing and marks nothing."""
+    from animateportrait_amd import losses
+    size, far = 33, float(2 ** 21)
+    g = torch.Generator().manual_seed(2100 + thickness)
+    lands = torch.rand(3, 22, 2, generator=g) * (size * 1.6) - size * 0.3
+    lands[0, 20:] = torch.tensor([[-4096.0, -4090.0], [4096.0, 4120.0]])
+    lands[2, 20:] = torch.tensor([[4096.0, -4096.0], [-4096.0, 4111.0]])
+    lands[1, :, 0] = -far
+    lands[1, :, 1] = torch.where(torch.arange(22) % 3 == 0, -far, far)
+    lands[1, 5] = torch.tensor([float('nan'), float('nan')])
+    segs = [(i, (i + 1) % 20) for i in range(20)] + [(20, 21)]
+    got = losses.lip_line_mask(lands.to(dev), segs, size, thickness).cpu()[:, 0].numpy()
+    want = _lip_oracle(size, lands[[0, 2]], segs, thickness)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[2], want[1])
+    assert want[0].sum() > 0 and want[1].sum() > 0
+    assert float(np.abs(got[1]).sum()) == 0.0 and not np.isnan(got).any()
+
+
+def test_landmark_discs_far_and_nan_points_contribute_nothing(dev):
+    """40 x 72, radius 5: points at +-2^21 and one NaN among in-range ones.  The map equals oracle.aux_glue.draw2 of the
+    in-range points alone (the far ones land on the coordinate clamp, far outside every canvas)."""
+    from animateportrait_amd import losses
+    from oracle import aux_glue as oa
+    h, w, radius, far = 40, 72, 5, float(2 ** 21)
+    lm = _disc_points(h, w, torch.Generator().manual_seed(2021))
+    hostile = {1: [far, 20.0], 4: [30.0, -far], 6: [-far, far], 9: [float('nan'), 12.0], 10: [far, far]}
+    keep = [i for i in range(12) if i not in hostile]
+    full = lm.clone()
+    for i, p in hostile.items():
+        full[:, i] = torch.tensor(p)
+    out = losses.landmark_discs(full.to(dev), h, w, radius).cpu()
+    for i in range(3):
+        want = oa.draw2(h, w, lm[i, keep].numpy(), radius)
+        assert torch.equal(out[i], want), i
+        assert float((want > 0).sum()) > 0
+    assert not bool(torch.equal(out[0], oa.draw2(h, w, lm[0].numpy(), radius)))      # the replaced points did mark pixels
 
 
 # ------------------------------------------------------------------------------------------------------- reductions, axpy

@@ -1,16 +1,17 @@
-// The rasteriser of apd_landmark_map (animateportrait_amd/csrc/data/landmark_raster.h) compiled for the host: reads cases,
-// evaluates every pixel through the same predicates the kernel uses, row tile by row tile as the kernel does, and writes
-// the maps.  tools/raster_host_check.py builds it with -fsanitize=address,undefined, feeds it and compares with
+// The rasteriser of apd_landmark_map and ap_lip_line_mask (animateportrait_amd/csrc/cv_raster.h) compiled for the host: reads
+// cases, evaluates every pixel through the same predicates the kernels use, row tile by row tile as the kernels do, and
+// writes the maps.  tools/raster_host_check.py builds it with -fsanitize=address,undefined, feeds it and compares with
 // oracle/cv_raster.
 //
 // input  (binary, native endian), repeated until EOF:  int32 H, W, P, S, radius, thickness, op;  float32 lm[P][2];  int32 seg[S][2]
+//         op 0 / 1: draw2 (discs / discs and lines, rounded points);  op 2: the lip mask (lines only, truncated points)
 // output: uint8 map[H][W] per case (1 on a mark)
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <vector>
 
-#include "../animateportrait_amd/csrc/data/landmark_raster.h"
+#include "../animateportrait_amd/csrc/cv_raster.h"
 
 using namespace apd_raster;
 
@@ -29,10 +30,11 @@ int main(int argc, char** argv) {
         if (fread(lm.data(), sizeof(float), lm.size(), in) != lm.size()) return 3;
         if (S && fread(seg.data(), sizeof(int32_t), seg.size(), in) != seg.size()) return 3;
         std::vector<int> pts(2 * P);
-        for (int i = 0; i < 2 * P; ++i) pts[i] = round_coord(lm[i]);
+        for (int i = 0; i < 2 * P; ++i) pts[i] = op == 2 ? trunc_coord(lm[i]) : round_coord(lm[i]);
         const int rad = cap_radius(thickness);
         const CircleRows disc = circle_rows(radius), cap = circle_rows(rad);
-        std::vector<Segment> segs(op == 1 ? S : 0);
+        const int discs = op == 2 ? 0 : P;
+        std::vector<Segment> segs(op >= 1 ? S : 0);
         std::vector<unsigned char> map((size_t)H * W);
         for (int row0 = 0; row0 < H; row0 += TH) {
             const int row1 = row0 + TH < H ? row0 + TH : H;
@@ -43,7 +45,7 @@ int main(int argc, char** argv) {
             for (int y = row0; y < row1; ++y)
                 for (int x = 0; x < W; ++x) {
                     bool hit = false;
-                    for (int i = 0; i < P && !hit; ++i) hit = circle_covers(disc, radius, pts[2 * i], pts[2 * i + 1], x, y);
+                    for (int i = 0; i < discs && !hit; ++i) hit = circle_covers(disc, radius, pts[2 * i], pts[2 * i + 1], x, y);
                     for (size_t s = 0; s < segs.size() && !hit; ++s) hit = segment_covers(segs[s], cap, rad, x, y);
                     map[(size_t)y * W + x] = hit;
                 }

@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
-"""Builds tools/raster_host_check.cpp (the predicates of apd_landmark_map compiled for the host) with
--fsanitize=address,undefined, runs the rasteriser cases of tests/testset_fixture.py -- and the 64-segment table on the
-fixture landmarks at 256 x 256 -- through it and compares every map with draw2 restated on oracle/cv_raster.
+"""Builds tools/raster_host_check.cpp (the predicates of csrc/cv_raster.h compiled for the host) with
+-fsanitize=address,undefined and runs two families of cases through it:
+
+  * draw2 (apd_landmark_map): the rasteriser cases of tests/testset_fixture.py -- and the 64-segment table on the fixture
+    landmarks at 256 x 256 and 512 x 512 -- compared with draw2 restated on oracle/cv_raster;
+  * the lip mask (ap_lip_line_mask: truncated points, lines only): the model's LIP_SEGMENTS on seeded lip loops that leave
+    the frame, a zero-length segment, the literal lines of tests/golden/opencv_rules.json and a segment from -4096 to +4096
+    across a 33-pixel canvas, compared with oracle/cv_raster.lip_line_mask (the literal lines with their committed runs);
+    and segments whose end points are +-2^21, NaN or +-inf on one side of the canvas, which must contribute nothing.
 
     python tools/raster_host_check.py [--cxx g++]
 """
 import argparse
+import json
 import os
 import subprocess
 import sys
@@ -18,8 +25,64 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 
-def main():
+def draw2_runs():
     import testset_fixture as tf
+    cases = dict(tf.raster_cases())
+    rng = np.random.RandomState(1)
+    lm = np.stack([np.linspace(60, 200, 68) + rng.uniform(-20, 20, 68), 128 + 70 * np.sin(np.arange(68)) + rng.uniform(-5, 5, 68)], 1)
+    cases['table256'] = (256, 256, lm.astype(np.float32), np.load(tf.LOOKUP).astype(np.int32), 3, 2)
+    cases['table512'] = (512, 512, (2 * lm).astype(np.float32), np.load(tf.LOOKUP).astype(np.int32), 5, 4)
+    runs = []
+    for name, (h, w, pts, seg, radius, thickness) in sorted(cases.items()):
+        for op in (0, 1):
+            want = (lambda h=h, w=w, pts=pts, seg=seg, radius=radius, thickness=thickness, op=op:
+                    tf.draw2_reference(pts, seg, h, w, radius, thickness, op) > 0)
+            runs.append((name, op, h, w, pts, seg, radius, thickness, want))
+    return runs
+
+
+def lip_runs():
+    """(name, 2, size, size, points, segments, 0, thickness, expected map) of the lip-mask mode.  ``drawn`` are the segments the
+    oracle draws; every other segment of a case has to contribute nothing."""
+    from animateportrait_amd.models.geomgm_ifw_fore_model import LIP_SEGMENTS
+    from oracle import cv_raster as cr
+    runs = []
+
+    def case(name, size, pts, seg, thickness, drawn=None):
+        pts = np.asarray(pts, np.float32)
+        drawn = seg if drawn is None else drawn
+        runs.append((name, 2, size, size, pts, seg, 0, thickness,
+                     lambda: cr.lip_line_mask(size, pts.astype(np.float64), drawn, thickness) > 0))
+
+    rng = np.random.RandomState(2)
+    for size in (64, 33):
+        for thickness in (2, 3, 15, 16):
+            # on and off the frame, negative coordinates included: int() truncates toward zero
+            case('lip%d_t%d' % (size, thickness), size, rng.uniform(-0.3 * size, 1.3 * size, (68, 2)), LIP_SEGMENTS, thickness)
+    for thickness in (2, 3):
+        case('zero_length_t%d' % thickness, 33, [[10.7, 12.2], [10.2, 12.9]], [(0, 1)], thickness)
+    for thickness in (2, 16):
+        case('long_t%d' % thickness, 33, [[-4096.0, -4090.0], [4096.0, 4120.0]], [(0, 1)], thickness)
+    d = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'opencv_rules.json')))
+    for i, ln in enumerate(d['lines']):
+        want = np.zeros((d['canvas'], d['canvas']), bool)
+        for y, a, b in ln['runs']:
+            want[y, a:b + 1] = True
+        pts = np.array([ln['p0'], ln['p1']], np.float32) + 0.4
+        runs.append(('golden_line%d' % i, 2, d['canvas'], d['canvas'], pts, [(0, 1)], 0, ln['thickness'], lambda want=want: want))
+    far, nan, inf = float(2 ** 21), float('nan'), float('inf')
+    loop = rng.uniform(-4, 37, (20, 2)).tolist()
+    near = [(i, (i + 1) % 20) for i in range(20)]
+    beyond = [[-far, 5], [-far, 20], [far, -far], [far, far], [5, -far], [20, -far], [-far, far], [far, far],
+              [nan, 10], [-far, 12], [nan, nan], [-far, -far], [inf, 3], [far, 30], [10, -inf], [20, -far]]
+    off = [(20 + 2 * i, 21 + 2 * i) for i in range(len(beyond) // 2)]
+    for thickness in (2, 16):
+        case('far_nan_inf_t%d' % thickness, 33, loop + beyond, near[:12] + off + near[12:], thickness, drawn=near)
+        case('only_far_t%d' % thickness, 33, loop + beyond, off, thickness, drawn=[])
+    return runs
+
+
+def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cxx', default='g++')
     args = ap.parse_args()
@@ -27,29 +90,26 @@ def main():
     exe = os.path.join(work, 'raster_host_check')
     subprocess.check_call([args.cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
                            '-ffp-contract=off', os.path.join(ROOT, 'tools', 'raster_host_check.cpp'), '-o', exe])
-    cases = dict(tf.raster_cases())
-    rng = np.random.RandomState(1)
-    lm = np.stack([np.linspace(60, 200, 68) + rng.uniform(-20, 20, 68), 128 + 70 * np.sin(np.arange(68)) + rng.uniform(-5, 5, 68)], 1)
-    cases['table256'] = (256, 256, lm.astype(np.float32), np.load(tf.LOOKUP).astype(np.int32), 3, 2)
-    cases['table512'] = (512, 512, (2 * lm).astype(np.float32), np.load(tf.LOOKUP).astype(np.int32), 5, 4)
-    runs = [(name, op) + c for name, c in sorted(cases.items()) for op in (0, 1)]
-    with open(os.path.join(work, 'cases.bin'), 'wb') as f:
-        for name, op, h, w, pts, seg, radius, thickness in runs:
-            f.write(np.array([h, w, len(pts), len(seg), radius, thickness, op], np.int32).tobytes())
-            f.write(np.ascontiguousarray(pts, np.float32).tobytes())
-            f.write(np.ascontiguousarray(seg, np.int32).tobytes())
-    subprocess.check_call([exe, os.path.join(work, 'cases.bin'), os.path.join(work, 'maps.bin')])
-    got = np.fromfile(os.path.join(work, 'maps.bin'), np.uint8)
-    at, bad = 0, 0
-    for name, op, h, w, pts, seg, radius, thickness in runs:
-        g = got[at:at + h * w].reshape(h, w)
-        at += h * w
-        want = tf.draw2_reference(pts, seg, h, w, radius, thickness, op) > 0
-        diff = int((g.astype(bool) != want).sum())
-        bad += diff
-        print('%-22s op %d: %5d marked, %d pixels differ' % (name, op, int(want.sum()), diff))
-    assert at == got.size
-    print('FAILED' if bad else 'all maps equal')
+    bad = 0
+    for what, runs in (('maps', draw2_runs()), ('lip masks', lip_runs())):
+        with open(os.path.join(work, 'cases.bin'), 'wb') as f:
+            for name, op, h, w, pts, seg, radius, thickness, want in runs:
+                f.write(np.array([h, w, len(pts), len(seg), radius, thickness, op], np.int32).tobytes())
+                f.write(np.ascontiguousarray(pts, np.float32).tobytes())
+                f.write(np.ascontiguousarray(seg, np.int32).tobytes())
+        subprocess.check_call([exe, os.path.join(work, 'cases.bin'), os.path.join(work, 'maps.bin')])
+        got = np.fromfile(os.path.join(work, 'maps.bin'), np.uint8)
+        at, wrong = 0, 0
+        for name, op, h, w, pts, seg, radius, thickness, want in runs:
+            g = got[at:at + h * w].reshape(h, w)
+            at += h * w
+            want = want()
+            diff = int((g.astype(bool) != want).sum())
+            wrong += diff
+            print('%-22s op %d: %5d marked, %d pixels differ' % (name, op, int(want.sum()), diff))
+        assert at == got.size
+        print('FAILED: %s differ' % what if wrong else 'all %s equal' % what)
+        bad += wrong
     return 1 if bad else 0
 
 
