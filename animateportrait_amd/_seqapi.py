@@ -1,6 +1,7 @@
 """ctypes binding of libapseq.so (C ABI declared in include/animateportrait_seq.h): the batched LSTM forward of Module1's
 landmark networks, the clip-level post-processing of their landmark sequence, the clip's f0 track (f0.py), the two ends of
-its speaker embedding (speaker.py) and its audio front end (audio_device.py).  Separate from _capi.py / libapamd.so, the boundary a model integrator binds.
+its speaker embedding (speaker.py), its audio front end (audio_device.py) and the pose network's self-attention encoder
+(encoder_hip.py).  Separate from _capi.py / libapamd.so, the boundary a model integrator binds.
 Loaded on first use; as there, a missing library or a failed call raises -- there is no silent fallback."""
 import ctypes
 import os
@@ -22,6 +23,7 @@ F0_HOP, F0_CANDS, F0_STATES, F0_MIN_LAG, F0_MAX_LAG, F0_UNVOICED = 256, 19, 20, 
 MEL_MIN_FFT, MEL_MAX_FFT, MEL_MAX_MELS, ALIGN_F64, SPK_E, SPK_MAX_B = 16, 1024, 128, 8, 256, 4096
 RS_MAX_RATE, RS_MAX_TAPS, RS_MAX_C, RS_MAX_L = 1024, 16384, 2, 0x3fffffff
 LOUD_MAX_N, LOUD_MAX_BLOCKS, FF_MAX_M, FF_MAX_L, FF_TILE = 8388607, 256, 8, 0x3fffffc0, 1024
+ENC_D, ENC_HEADS, ENC_ROWS, ENC_MAX_T, ENC_FF_CHUNK, ENC_MAX_FF = 64, 2, 16, 512, 256, 8192
 
 _i32, _i64, _ptr, _f32, _f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
 # name -> (restype, argtypes); every symbol include/animateportrait_seq.h declares
@@ -67,6 +69,11 @@ SIGNATURES = {
     'apq_filtfilt': (ctypes.c_int, [_ptr] * 6 + [_i32] * 2 + [_ptr]),
     'apq_logmel_frames_ok': (_i32, [_ptr] * 4 + [_i32] * 4),
     'apq_logmel_frames': (ctypes.c_int, [_ptr] * 4 + [_i32] * 4 + [_ptr]),
+    # the pose network's self-attention encoder (encoder_hip.py)
+    'apq_enc_qkv_ok': (_i32, [_ptr] * 3 + [_f32] + [_ptr] * 9 + [_i32] * 3),
+    'apq_enc_qkv': (ctypes.c_int, [_ptr] * 3 + [_f32] + [_ptr] * 9 + [_i32] * 3 + [_ptr]),
+    'apq_enc_attn_ff_ok': (_i32, [_ptr] * 8 + [_f32] + [_ptr] * 6 + [_f32, _ptr] + [_i32] * 5),
+    'apq_enc_attn_ff': (ctypes.c_int, [_ptr] * 8 + [_f32] + [_ptr] * 6 + [_f32, _ptr] + [_i32] * 5 + [_ptr]),
 }
 
 _lib = None

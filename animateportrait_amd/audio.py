@@ -146,16 +146,40 @@ def window_frames(au, num_window_frames=WINDOW_FRAMES, step=1):
     return np.stack([au[i:i + num_window_frames] for i in range(0, n, step)])
 
 
-def clip_audio_features(path, max_frames=None, normalize=True, converter=None, backend='host'):
+def load_mean_std(path):
+    """The reference's mel normalisation table (MEAN_STD_AUTOVC_RETRAIN_MEL_AU.txt, audio2landmark_dataset.py:47-53): a text file
+    whose first half holds the means and whose second half the standard deviations.  Returns (mean, std) in float64."""
+    ms = np.loadtxt(path)
+    return ms[0:ms.shape[0] // 2], ms[ms.shape[0] // 2:]
+
+
+def normalize_mel(s, mean_std):
+    """``(au - au_mean) / au_std`` on a (T, 80) mel, a host array or a CUDA tensor alike: computed in float64, returned in float32.
+    ``mean_std``: a table's path or its (mean, std); None returns ``s`` itself."""
+    if mean_std is None:
+        return s
+    mean, std = load_mean_std(mean_std) if isinstance(mean_std, (str, bytes)) or hasattr(mean_std, '__fspath__') else mean_std
+    if s.shape[-1] != len(mean) or len(mean) != len(std):
+        raise ValueError('normalize_mel: a table of %d means and %d standard deviations for a mel of %d bands' % (len(mean), len(std), s.shape[-1]))
+    import torch
+    if torch.is_tensor(s):
+        m, d = (torch.as_tensor(np.asarray(v, dtype=np.float64), device=s.device) for v in (mean, std))
+        return ((s.double() - m) / d).float()
+    return ((np.asarray(s, dtype=np.float64) - mean) / std).astype(np.float32)
+
+
+def clip_audio_features(path, max_frames=None, normalize=True, converter=None, backend='host', au_mean_std=None):
     """wav file -> float32 windows (F, 18, 80) for ``module1.predict_landmarks*``; F output frames at 62.5 fps.
     converter: the AutoVC stage between the mel spectrogram and the windows (main_end2end_module2.py:218-224), a callable
     (T, 80) mel -> (T, 80) mel -- ``lambda mel: autovc.convert_mel(G, mel, f0, emb_src, emb_trg)``.  None hands the RAW mel to
     the windows, which is NOT what checkpoints trained by the reference expect (they saw converted spectrograms).
+    au_mean_std: the reference's normalisation table (a path, or (mean, std)): the windows are cut from (mel - mean) / std of the
+    converted mel, as the reference's test-time dataset does; None (default) leaves the mel as it is.
     backend: 'host' = numpy / scipy here; 'device' = audio_device.py (libapseq.so): a float32 CUDA tensor of windows, the converter
     is called with the device mel; a clip the device does not serve is computed here after a printed notice."""
     if backend == 'device':
         from . import audio_device
-        return audio_device.clip_audio_features(path, max_frames, normalize, converter)
+        return audio_device.clip_audio_features(path, max_frames, normalize, converter, au_mean_std=au_mean_std)
     if backend != 'host':
         raise ValueError("audio.clip_audio_features: backend %r (known: 'host', 'device')" % (backend,))
     x, sr = read_wav(path)
@@ -165,5 +189,5 @@ def clip_audio_features(path, max_frames=None, normalize=True, converter=None, b
     s = mel_spectrogram(x).astype(np.float32)
     if converter is not None:
         s = np.asarray(converter(s), dtype=np.float32)
-    w = window_frames(s)
+    w = window_frames(normalize_mel(s, au_mean_std))
     return w if max_frames is None else w[:max_frames]

@@ -283,19 +283,19 @@ class ClipAudio:
         return self._get('tracker_input', lambda: self.conditioned.to(torch.float32) * 32768)
 
 
-def clip_audio_features(path, max_frames=None, normalize=True, converter=None, device=None):
+def clip_audio_features(path, max_frames=None, normalize=True, converter=None, device=None, au_mean_std=None):
     """``audio.clip_audio_features(..., backend='device')``: the windows (F, 18, 80) as a float32 CUDA tensor.  ``path`` may be a
     ``ClipAudio``.  The converter is called with the device mel and may return a tensor or an array.  A clip the device does not
-    serve gives the host's windows (numpy), after ClipAudio's notice."""
+    serve gives the host's windows (numpy), after ClipAudio's notice.  ``au_mean_std``: as in ``audio.clip_audio_features``."""
     clip = path if isinstance(path, ClipAudio) else ClipAudio(path, device=device, normalize=normalize)
     if not clip.on_device:
         s = clip._host_stage('mel')
         if converter is not None:
             s = np.asarray(converter(s), dtype=np.float32)
-        w = audio.window_frames(s)
+        w = audio.window_frames(audio.normalize_mel(s, au_mean_std))
         return w if max_frames is None else w[:max_frames]
     s = clip.mel()
     if converter is not None:
         s = torch.as_tensor(converter(s), dtype=torch.float32, device=s.device)
-    w = window_frames_device(s)
+    w = window_frames_device(audio.normalize_mel(s, au_mean_std))
     return (w if max_frames is None else w[:max_frames]).contiguous()

@@ -110,6 +110,8 @@ def landmarks_from_audio(a, device):
         module1.set_lstm_backend(a.module1_lstm)
     if a.module1_post is not None:
         module1.set_post_backend(a.module1_post)
+    if getattr(a, 'module1_encoder', None) is not None:
+        module1.set_encoder_backend(a.module1_encoder)
     if a.speaker_emb_from == 'wav':
         # main_end2end_module2.py:216-219: the clip's own embedding, before the converter; it conditions both stages below
         from . import speaker
@@ -145,9 +147,9 @@ def landmarks_from_audio(a, device):
                   'pysptk, which is not in this image)')
         converter = lambda mel: autovc.convert_mel(G, mel, None if f0 is None else f0[:mel.shape[0]], emb, emb_trg, device)   # noqa: E731
     if clip is not None:
-        windows = audio_device.clip_audio_features(clip, max_frames=a.max_frames, converter=converter)
+        windows = audio_device.clip_audio_features(clip, max_frames=a.max_frames, converter=converter, au_mean_std=getattr(a, 'au_mean_std', None))
     else:
-        windows = audio.clip_audio_features(a.wav, max_frames=a.max_frames, converter=converter)
+        windows = audio.clip_audio_features(a.wav, max_frames=a.max_frames, converter=converter, au_mean_std=getattr(a, 'au_mean_std', None))
     fl = module1.predict_landmarks_speaker_aware(net_g, net_c, windows, emb, face_id.reshape(-1))
     seq = module1.to_image_landmarks(fl, scale=scale, shift=shift)[:, :, :2]
     if torch.is_tensor(seq):
@@ -204,6 +206,13 @@ def make_parser():
     ap.add_argument('--module1_lstm', choices=('library', 'hip'), default=None,
                     help='who runs the LSTMs of the two Module1 networks: library = nn.LSTM, hip = the batched kernel of '
                          'libapseq.so, one launch per layer (default: library, or what APAMD_MODULE1_LSTM names)')
+    ap.add_argument('--module1_encoder', choices=('library', 'hip'), default=None,
+                    help='who runs the self-attention encoder of Module1\'s pose network: library = the torch modules, hip = two '
+                         'launches per layer of libapseq.so (default: library, or what APAMD_MODULE1_ENCODER names)')
+    ap.add_argument('--au_mean_std', default=None,
+                    help='table of mel means and standard deviations (the reference\'s MEAN_STD_AUTOVC_RETRAIN_MEL_AU.txt: 80 means, '
+                         'then 80 standard deviations): Module1 is fed (mel - mean) / std of the converted spectrogram, as the '
+                         'reference\'s test-time dataset feeds it (default: none, the unnormalised mel)')
     ap.add_argument('--module1_post', choices=('host', 'device'), default=None,
                     help='where Module1\'s landmark post-processing runs (Savitzky-Golay filters, baseline calibration, lip fixes, '
                          'eye lids): host = numpy / scipy, device = libapseq.so, the landmark sequence then stays on the GPU; with '

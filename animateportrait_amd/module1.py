@@ -16,7 +16,8 @@ APAMD_MODULE1_LSTM=hip) moves their LSTMs to the batched kernel of libapseq.so. 
 235-245, 247-309, 594-617) followed by the clip-level post-processing of main_end2end_module2.py:262-272; the simpler
 ``predict_landmarks`` is the content branch alone (``__train_face_wo_pos__``).  That post-processing is numpy / scipy on the host
 by default; ``set_post_backend('device')`` (or APAMD_MODULE1_POST=device) runs it in libapseq.so (landmark_post.py) and keeps the
-landmark sequence on the GPU.  Training the content branch is module1_train.py; ``set_lstm_train_backend('hip')`` (or
+landmark sequence on the GPU.  ``set_encoder_backend('hip')`` (or APAMD_MODULE1_ENCODER=hip) runs the pose network's self-attention
+encoder as two launches per layer of libapseq.so (encoder_hip.py).  Training the content branch is module1_train.py; ``set_lstm_train_backend('hip')`` (or
 APAMD_MODULE1_LSTM_TRAIN=hip) puts its LSTM on the training kernel pair of libapseq.so.  NOT built: the AutoVC mel / speaker
 embedding front end (librosa / pysptk / pyworld / resemblyzer are not in this image, and neither are the checkpoints);
 callers pass the (T, 18, 80) mel windows and the 256-d speaker embedding the reference's ``au_data`` / ``au_emb`` hold.
@@ -100,6 +101,32 @@ def set_lstm_train_backend(name):
 
 def get_lstm_train_backend():
     return _lstm_train_backend
+
+
+# Who runs the pose network's self-attention encoder at inference on the device: 'library' = the torch modules below, 'hip' = two
+# launches per layer of libapseq.so (encoder_hip.encoder_forward: apq_enc_qkv, apq_enc_attn_ff).  CPU tensors, a mask and training
+# with gradients always take the torch modules.
+ENCODER_BACKENDS = ('library', 'hip')
+
+
+def _checked_encoder_backend(name):
+    if name not in ENCODER_BACKENDS:
+        raise ValueError('Module1 encoder backend %r (known: %s)' % (name, ', '.join(ENCODER_BACKENDS)))
+    return name
+
+
+_encoder_backend = _checked_encoder_backend(os.environ.get('APAMD_MODULE1_ENCODER') or 'library')
+
+
+def set_encoder_backend(name):
+    """Select who runs ``Encoder.forward`` at inference; returns the previous backend."""
+    global _encoder_backend
+    prev, _encoder_backend = _encoder_backend, _checked_encoder_backend(name)
+    return prev
+
+
+def get_encoder_backend():
+    return _encoder_backend
 
 
 def _lstm_last(lstm, x, trainable=False):
@@ -255,11 +282,23 @@ class _Stack(nn.Module):                                                        
         self.norm = Norm(d_model)
 
 
+def _encoder_on_kernels(encoder, x, mask):
+    """Does ``Encoder.forward`` take the kernels of libapseq.so?  Only with the 'hip' backend, a CUDA tensor, no mask, gradients
+    disabled or the module in eval mode, and shapes the library serves (encoder_hip.supported: its host-only ``_ok`` calls)."""
+    if not (_encoder_backend == 'hip' and x.is_cuda and mask is None and not (torch.is_grad_enabled() and encoder.training)):
+        return False
+    from . import encoder_hip
+    return encoder_hip.supported(encoder, x)
+
+
 class Encoder(_Stack):
     def __init__(self, d_model, n, heads, in_size):
         super().__init__(EncoderLayer(d_model, heads), d_model, n, in_size)
 
     def forward(self, x, mask=None):
+        if _encoder_on_kernels(self, x, mask):
+            from . import encoder_hip
+            return encoder_hip.encoder_forward(self, x)
         x = self.pe(self.embed(x))
         for layer in self.layers:
             x = layer(x, mask)

@@ -31,6 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from . import module1
+from .audio import load_mean_std
 
 SEG_BS = 512          # windows of a segment (train_content.py:168)
 MIN_SEG = 10          # shorter segments are skipped (:204)
@@ -63,8 +64,7 @@ class ContentDataset:
         self.fl_data = [data['fl'][i] for i in idx]
         self.au_data = [data['au'][i] for i in idx]
         if au_mean_std is not None:
-            ms = np.loadtxt(au_mean_std)
-            mean, std = ms[0:ms.shape[0] // 2], ms[ms.shape[0] // 2:]
+            mean, std = load_mean_std(au_mean_std)
             self.au_data = [((au - mean) / std,) + tuple(rest) for au, *rest in self.au_data]
 
     def __len__(self):

@@ -15,7 +15,8 @@
  * enqueue on `stream` (a hipStream_t as void*), 0 = ok, negative = error with a thread-local message (apq_last_error()).
  * A refused call launches nothing and writes nothing; every launching call has a twin `<name>_ok` that needs no device.
  * The post-processing entry points were added without a change of APQ_ABI_VERSION: nothing that existed changed; so were the
- * clip's f0 track, the two ends of its speaker embedding and its audio front end (further down).
+ * clip's f0 track, the two ends of its speaker embedding, its audio front end and the two launches per layer of the pose
+ * network's self-attention encoder (further down).
  */
 #ifndef ANIMATEPORTRAIT_SEQ_H
 #define ANIMATEPORTRAIT_SEQ_H
@@ -280,6 +281,52 @@ int32_t apq_logmel_frames_ok(const double* x, const double* window, const float*
                              int32_t hop, int32_t n_mels);
 int apq_logmel_frames(const double* x, const double* window, const float* basis, float* out, int32_t L, int32_t n_fft, int32_t hop,
                       int32_t n_mels, void* stream);
+
+/* ------------------------------------------------------- the pose network's self-attention encoder (seq_encoder.hip)
+ * Encoder.forward of Module1/src/models/model_audio2landmark_speaker_aware.py (:195-209, its pieces :26-161) at inference, behind
+ * the embedding and the positional term: per layer the two launches below, as tests/encoder_reference.py states them in float64.
+ * Every product runs on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32, exact fp32 products, K walked in chunks of four); a
+ * workgroup owns 16 rows and talks to no other: no atomics, no spin, no workspace beyond q, k and v.  The weights keep nn.Linear's
+ * layout [out][in]; nothing is packed or cached.  No mask, no dropout.  Every pointer is 16-byte aligned (APQ_ALIGN_WIDE).  The
+ * `_ok` twins and the error codes follow the rules of apq_lstm_layer_fwd_ok.  Added without a change of APQ_ABI_VERSION:
+ * nothing that existed changed. */
+#define APQ_ENC_D 64            /* d_model: the one width built */
+#define APQ_ENC_HEADS 2         /* heads of d_k = 32 */
+#define APQ_ENC_ROWS 16         /* rows of a workgroup */
+#define APQ_ENC_MAX_T 512       /* rows of a sequence (PositionalEncoder's table): a tile's 2 x 16 x T scores live in LDS */
+#define APQ_ENC_FF_CHUNK 256    /* d_ff is walked in chunks of this many hidden units: d_ff is a multiple of it */
+#define APQ_ENC_MAX_FF 8192     /* d_ff */
+
+/* Norm_1 and the three projections of a layer for all B T rows, one launch of ceil(B T / 16) workgroups:
+ *   n = alpha (x - mean) / (std + eps) + bias per row, std unbiased (divided by 63), eps added to the std
+ *   q = n wq^T + bq,  k = n wk^T + bk,  v = n wv^T + bv
+ *   x [B][T][64];  alpha, bias [64];  wq, wk, wv [64][64];  bq, bk, bv [64];  q, k, v [B][T][64] (the caller's workspace)
+ * 1 <= T <= APQ_ENC_MAX_T, 1 <= B <= APQ_MAX_B, B T 64 below 2^31, d_model == APQ_ENC_D. */
+int32_t apq_enc_qkv_ok(const float* x, const float* alpha, const float* bias, float eps, const float* wq, const float* bq,
+                       const float* wk, const float* bk, const float* wv, const float* bv, const float* q, const float* k,
+                       const float* v, int32_t B, int32_t T, int32_t d_model);
+int apq_enc_qkv(const float* x, const float* alpha, const float* bias, float eps, const float* wq, const float* bq, const float* wk,
+                const float* bk, const float* wv, const float* bv, float* q, float* k, float* v, int32_t B, int32_t T,
+                int32_t d_model, void* stream);
+
+/* The rest of EncoderLayer.forward, one launch of B ceil(T / 16) workgroups, each with 16 query rows of one sequence:
+ *   per head h: p = softmax(q_h k_h^T / sqrt(32)) over the T keys of the row's own sequence (maximum subtracted first),
+ *               c[:, 32 h : 32 h + 32] = p v_h                               (the heads side by side, head-major columns)
+ *   x1 = x + (c wo^T + bo),   n = Norm_2(x1) with alpha2, bias2, eps2
+ *   y  = x1 + (relu(n w1^T + b1) w2^T + b2)      (d_ff walked in chunks: the hidden activations stay in registers)
+ *   with alpha_f and bias_f non-null (both or neither): y = Norm(y) with alpha_f, bias_f, eps_f -- the encoder's closing Norm
+ *   x, q, k, v, y [B][T][64];  wo [64][64], bo [64];  w1 [d_ff][64], b1 [d_ff];  w2 [64][d_ff], b2 [64]
+ * Keys at and beyond T are never read.  y may be x (a workgroup reads only its own rows of x).  Served as apq_enc_qkv, with
+ * heads == APQ_ENC_HEADS and d_ff a multiple of APQ_ENC_FF_CHUNK up to APQ_ENC_MAX_FF.  The order of every sum is the same for
+ * every row and launch: a sequence's result does not depend on its place in the batch. */
+int32_t apq_enc_attn_ff_ok(const float* x, const float* q, const float* k, const float* v, const float* wo, const float* bo,
+                           const float* alpha2, const float* bias2, float eps2, const float* w1, const float* b1, const float* w2,
+                           const float* b2, const float* alpha_f, const float* bias_f, float eps_f, const float* y, int32_t B,
+                           int32_t T, int32_t d_model, int32_t heads, int32_t d_ff);
+int apq_enc_attn_ff(const float* x, const float* q, const float* k, const float* v, const float* wo, const float* bo,
+                    const float* alpha2, const float* bias2, float eps2, const float* w1, const float* b1, const float* w2,
+                    const float* b2, const float* alpha_f, const float* bias_f, float eps_f, float* y, int32_t B, int32_t T,
+                    int32_t d_model, int32_t heads, int32_t d_ff, void* stream);
 
 #ifdef __cplusplus
 }
