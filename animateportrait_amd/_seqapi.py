@@ -19,6 +19,7 @@ OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_LAUNCH = 0, -1, -2, -3
 LM_C, SG_MIN_W, SG_MAX_W, SEG_MAX_T, MAX_STAMPS = 204, 5, 31, 512, 4096
 SEG_CLOSE, SEG_LIP, SEG_NOSE = 1, 2, 4
 IMG_TRANSFORM, IMG_EYES = 1, 2
+REG_CENTER, REG_NO_X_ROT, REG_REGISTER, REG_MAX_ROUNDS = 1, 2, 4, 50
 F0_HOP, F0_CANDS, F0_STATES, F0_MIN_LAG, F0_MAX_LAG, F0_UNVOICED = 256, 19, 20, 2, 320, 255
 MEL_MIN_FFT, MEL_MAX_FFT, MEL_MAX_MELS, ALIGN_F64, SPK_E, SPK_MAX_B = 16, 1024, 128, 8, 256, 4096
 RS_MAX_RATE, RS_MAX_TAPS, RS_MAX_C, RS_MAX_L = 1024, 16384, 2, 0x3fffffff
@@ -46,6 +47,9 @@ SIGNATURES = {
     'apq_segment_assemble': (ctypes.c_int, [_ptr] * 4 + [_i32, _f64, _f32, _i32, _ptr]),
     'apq_image_landmarks_ok': (_i32, [_ptr] * 3 + [_i32] * 2 + [_f64] * 3 + [_i32]),
     'apq_image_landmarks': (ctypes.c_int, [_ptr] * 3 + [_i32] * 2 + [_f64] * 3 + [_i32, _ptr]),
+    # rigid registration of landmark frames (landmark_post.rigid_register)
+    'apq_rigid_register_ok': (_i32, [_ptr] * 4 + [_i32] * 2),
+    'apq_rigid_register': (ctypes.c_int, [_ptr] * 4 + [_i32] * 2 + [_ptr]),
     # the clip's f0 track (f0.py)
     'apq_f0_candidates_ok': (_i32, [_ptr] + [_i32] * 4 + [_ptr] * 5),
     'apq_f0_candidates': (ctypes.c_int, [_ptr] + [_i32] * 4 + [_ptr] * 5 + [_ptr]),

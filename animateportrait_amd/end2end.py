@@ -150,7 +150,9 @@ def landmarks_from_audio(a, device):
         windows = audio_device.clip_audio_features(clip, max_frames=a.max_frames, converter=converter, au_mean_std=getattr(a, 'au_mean_std', None))
     else:
         windows = audio.clip_audio_features(a.wav, max_frames=a.max_frames, converter=converter, au_mean_std=getattr(a, 'au_mean_std', None))
-    fl = module1.predict_landmarks_speaker_aware(net_g, net_c, windows, emb, face_id.reshape(-1))
+    fl = module1.predict_landmarks_speaker_aware(net_g, net_c, windows, emb, face_id.reshape(-1),
+                                                 centerize_face=bool(getattr(a, 'centerize_face', False)),
+                                                 no_y_rotation=bool(getattr(a, 'no_y_rotation', False)))
     seq = module1.to_image_landmarks(fl, scale=scale, shift=shift)[:, :, :2]
     if torch.is_tensor(seq):
         return module1.photo_landmarks_in_pixels(face_id, scale, shift), seq.contiguous()
@@ -201,6 +203,15 @@ def make_parser():
                     help='feed the RAW mel spectrogram to Module1 (NOT what the reference does: its checkpoints were trained on '
                          'AutoVC-converted spectrograms); for experiments with networks trained that way')
     ap.add_argument('--std_face', default=None, help='STD_FACE_LANDMARKS.txt (its depth column replaces the detected one)')
+    ap.add_argument('--centerize_face', action='store_true',
+                    help='head stabilisation (train_audio2landmark.py:312-317): move every predicted frame\'s 68-point mean onto '
+                         'that of the photo\'s normalised face (default: off)')
+    ap.add_argument('--no_y_rotation', action='store_true',
+                    help='head stabilisation (train_audio2landmark.py:319-338; the reference\'s name): register every predicted '
+                         'frame\'s nose-and-eye-corner T shape onto the photo\'s and take one Euler angle out of the head\'s '
+                         'rotation R = Rz(c) Ry(b) Rx(a).  The angle removed is a, the rotation about the x axis (the nod), not the '
+                         'one about y the name promises: the reference zeroes the first entry of scipy\'s extrinsic \'xyz\' triple.  '
+                         'With --module1_post device one launch of libapseq.so, else numpy / scipy (default: off)')
     ap.add_argument('--load_a2l_G_name', default='Module1/checkpoints/ckpt_speaker_branch.pth')
     ap.add_argument('--load_a2l_C_name', default='Module1/checkpoints/ckpt_content_branch.pth')
     ap.add_argument('--module1_lstm', choices=('library', 'hip'), default=None,

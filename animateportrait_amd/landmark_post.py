@@ -110,6 +110,25 @@ def solve_inverse_lip(fl):
     return segment_assemble(fl, close=False, lip=True)
 
 
+def rigid_register(fl, std, center=False, no_x_rot=False, register=False, pose=False, out=None):
+    """One apq_rigid_register launch on (T, 204) frames against ``std`` (204,), a wave per frame (csrc/seq/seq_register.hip):
+    ``module1.stabilise_head`` with ``center`` (centerize_face) and ``no_x_rot`` (the reference's no_y_rotation), or
+    ``module1.register_face`` on every frame with ``register`` (which excludes the other two).  ``out``: a contiguous (T, 204)
+    tensor to write into, ``fl`` itself for in place.  With ``pose`` also returns the (T, 3, 4) float64 [R | t] that
+    ``module1.icp_t_shape`` gives for every frame (after the centring, before any angle is removed)."""
+    x = _dev32(fl, 'rigid_register', Q.LM_C)
+    sd = _dev32(std.reshape(1, -1) if torch.is_tensor(std) else std, 'rigid_register', Q.LM_C)
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape):
+        raise ValueError('landmark_post.rigid_register: out must be a contiguous float32 CUDA tensor of the shape of fl')
+    ps = torch.empty((x.shape[0], 3, 4), dtype=torch.float64, device=x.device) if pose else None
+    flags = (Q.REG_CENTER if center else 0) | (Q.REG_NO_X_ROT if no_x_rot else 0) | (Q.REG_REGISTER if register else 0)
+    Q.check(Q.lib().apq_rigid_register(ops._ptr(x), ops._ptr(sd), ops._ptr(out), ops._ptr(ps), x.shape[0], flags, ops._stream()),
+            'rigid_register')
+    return (out, ps) if pose else out
+
+
 def image_landmarks(fl, scale=1.0, shift=(0.0, 0.0), transform=True, stamps=None):
     """One apq_image_landmarks launch on (T, 204) -> (T, 204): the pixel transform and, with ``stamps`` (a list of frames),
     ``add_naive_eye`` with its blinks at those frames."""

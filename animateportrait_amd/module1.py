@@ -431,14 +431,89 @@ def add_naive_eye(fl, rng=np.random):
     return fl
 
 
+# ------------------------------------------------------------------------------------------------- rigid registration
+T_SHAPE_IDX = (27, 28, 29, 30, 33, 36, 39, 42, 45)      # nose bridge, nose base, the four eye corners: the face's rigid part
+
+
+def _best_fit_transform(a, b):
+    """util/icp.py:5-55: the rigid map (R, t) of the points a (N, 3) onto b (N, 3), Kabsch through LAPACK's SVD; when the fit
+    would reflect, the direction of the smallest singular value is mirrored."""
+    ca, cb = a.mean(axis=0), b.mean(axis=0)
+    u, _, vt = np.linalg.svd((a - ca).T @ (b - cb))
+    r = vt.T @ u.T
+    if np.linalg.det(r) < 0:
+        vt[-1] *= -1
+        r = vt.T @ u.T
+    return r, cb - r @ ca
+
+
+def icp_t_shape(frame, std, max_iterations=50, tolerance=1e-4):
+    """``icp(frame[T shape], std[T shape])`` of util/icp.py:77-132, whose neighbour search is commented out: the points
+    correspond by index.  frame, std: 68 x 3 in any shape.  Returns the (3, 4) float64 [R | t] that maps frame onto std."""
+    idx = list(T_SHAPE_IDX)
+    a = np.asarray(frame, dtype=np.float64).reshape(68, 3)[idx]
+    b = np.asarray(std, dtype=np.float64).reshape(68, 3)[idx]
+    src, prev = a.copy(), 0.0
+    for _ in range(max_iterations):
+        err = np.sum((src - b) ** 2)
+        r, t = _best_fit_transform(src, b)
+        src = src @ r.T + t
+        if abs(prev - err) < tolerance:
+            break
+        prev = err
+    r, t = _best_fit_transform(a, src)
+    return np.hstack((r, t[:, None]))
+
+
+def register_face(frame, anchor):
+    """train_content.py:176-183 (``--use_reg_as_std``): the frame's 68 points moved by ``icp_t_shape(frame, anchor)``.
+    Rows are float32 in and out, float64 between.  Returns (204,) float32; a CUDA tensor goes through libapseq.so."""
+    if torch.is_tensor(frame) and frame.is_cuda:
+        from . import landmark_post as lp
+        return lp.rigid_register(frame.float().reshape(1, -1), torch.as_tensor(anchor, dtype=torch.float32, device=frame.device),
+                                 register=True).view(-1)
+    p = np.asarray(frame, dtype=np.float32).astype(np.float64).reshape(68, 3)
+    t34 = icp_t_shape(p, np.asarray(anchor, dtype=np.float32))
+    return (p @ t34[:, :3].T + t34[:, 3]).reshape(204).astype(np.float32)
+
+
+def stabilise_head(fl, std, centerize_face=False, no_y_rotation=False):
+    """The two head-stabilisation switches of the reference's test pass (train_audio2landmark.py:312-338) on (T, 204) landmarks,
+    in its order: ``centerize_face`` moves every frame's 68-point mean onto that of ``std``; ``no_y_rotation`` registers every
+    frame's T shape onto ``std``'s and, with the fitted rotation R = Rz(c) Ry(b) Rx(a) and translation t, maps every point to
+    Rz(c) Ry(b) (p - t) + t -- the angle set to zero is the first of scipy's extrinsic 'xyz' triple, whatever the switch's name
+    says.  Rows are float32 in and out, float64 between.  numpy in, numpy out; a CUDA tensor is served by one launch of
+    libapseq.so (landmark_post.rigid_register) and stays on the device.  With both switches off ``fl`` is returned as it is."""
+    if not (centerize_face or no_y_rotation):
+        return fl
+    if torch.is_tensor(fl) and fl.is_cuda:
+        from . import landmark_post as lp
+        std = torch.as_tensor(std, dtype=torch.float32, device=fl.device).reshape(-1)
+        return lp.rigid_register(fl.float().reshape(-1, FACE_ID_FEAT_SIZE), std, center=centerize_face, no_x_rot=no_y_rotation)
+    from scipy.spatial.transform import Rotation
+    x = np.asarray(fl, dtype=np.float32).astype(np.float64).reshape(-1, 68, 3)
+    sd = np.asarray(std.detach().cpu() if torch.is_tensor(std) else std, dtype=np.float32).astype(np.float64).reshape(68, 3)
+    if centerize_face:
+        x = x - x.mean(axis=1, keepdims=True) + sd.mean(axis=0)
+    if no_y_rotation:
+        for i in range(x.shape[0]):
+            t34 = icp_t_shape(x[i], sd)
+            t = t34[:, 3]
+            _, b, c = Rotation.from_matrix(t34[:, :3]).as_euler('xyz')
+            x[i] = (x[i] - t) @ Rotation.from_euler('xyz', [0.0, b, c]).as_matrix().T + t
+    return x.reshape(-1, FACE_ID_FEAT_SIZE).astype(np.float32)
+
+
 @torch.no_grad()
 def predict_landmarks_speaker_aware(net_g, net_c, au_windows, spk_emb, face_id, amp_pos=0.5, amp_lip_x=2.0, amp_lip_y=2.0,
-                                    segment=512, smooth_win=31, close_mouth_ratio=0.99):
+                                    segment=512, smooth_win=31, close_mouth_ratio=0.99, centerize_face=False,
+                                    no_y_rotation=False):
     """``Audio2landmark_model.test`` (train_audio2landmark.py:247-309 with __train_face_and_pos__ :101-141):
     au_windows (T, 18, 80), spk_emb (256,), face_id (204,) -> (T, 204) landmarks in Module1's normalised frame.
     Per 512-window segment: pose branch G (speaker embedding x 3, z = 0) -> Savitzky-Golay over the segment -> lips
     pulled together -> x amp_pos; content branch C on the first 18 frames -> calibrated; sum + face id; inverted-lip fix.
-    Then the nose-top extrapolation and a (5, 3) Savitzky-Golay over the clip.
+    Then the nose-top extrapolation and a (5, 3) Savitzky-Golay over the clip, and behind it ``stabilise_head`` against ``face_id``
+    when ``centerize_face`` or ``no_y_rotation`` is set (:312-338; off, as in the reference's readme, nothing more runs).
     With the 'device' post-processing backend and networks on the GPU the result is a (T, 204) CUDA tensor and nothing between
     the windows and it touches the host; otherwise a numpy array."""
     net_g.eval()
@@ -448,8 +523,9 @@ def predict_landmarks_speaker_aware(net_g, net_c, au_windows, spk_emb, face_id, 
     emb = torch.as_tensor(spk_emb, dtype=torch.float32, device=dev).view(1, -1).expand(au.shape[0], -1)
     fid = torch.as_tensor(face_id, dtype=torch.float32, device=dev).view(1, FACE_ID_FEAT_SIZE)
     if _post_backend == 'device' and dev.type == 'cuda':
-        return _speaker_aware_on_device(net_g, net_c, au, emb, fid, amp_pos, amp_lip_x, amp_lip_y, segment, smooth_win,
-                                        close_mouth_ratio)
+        fl = _speaker_aware_on_device(net_g, net_c, au, emb, fid, amp_pos, amp_lip_x, amp_lip_y, segment, smooth_win,
+                                      close_mouth_ratio)
+        return stabilise_head(fl, fid.view(-1), centerize_face, no_y_rotation)
     out = []
     for j in range(0, au.shape[0], segment):
         a, e = au[j:j + segment], emb[j:j + segment]
@@ -464,7 +540,7 @@ def predict_landmarks_speaker_aware(net_g, net_c, au_windows, spk_emb, face_id, 
         out.append(solve_inverse_lip(seg))
     fl = np.concatenate(out)
     fl[:, 27 * 3:28 * 3] = fl[:, 28 * 3:29 * 3] * 2 - fl[:, 29 * 3:30 * 3]       # revise the nose top point (:300)
-    return _savgol(fl, 5)
+    return stabilise_head(_savgol(fl, 5), fid.cpu().numpy().reshape(-1), centerize_face, no_y_rotation)
 
 
 def _speaker_aware_on_device(net_g, net_c, au, emb, fid, amp_pos, amp_lip_x, amp_lip_y, segment, smooth_win, close_mouth_ratio):

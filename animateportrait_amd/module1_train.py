@@ -16,8 +16,11 @@ counterpart of Module1/src/approaches/train_content.py and its dataset, Module1/
 * ``--lstm hip`` trains the 3-layer LSTM on libapseq.so's kernel pair: ``main`` sets ``module1.set_lstm_train_backend`` for the run and
   restores it; ``ContentTrainer`` itself leaves the switch to its caller.
 
-NOT built: ``--use_reg_as_std`` (the ICP registration of the identity frame) is refused by name, and the ``Vis`` animation dumps
-(:226-251) do not exist.  The reference's launcher for this class is not in its tree; DESIGN.md 4e-5 says where the defaults
+* ``--use_reg_as_std --std_face FILE`` registers every clip's identity frame onto the standard face before it is used
+  (:176-183; ``module1.register_face`` on the host, one frame per clip): FILE is the reference's STD_FACE_LANDMARKS.txt, 68 rows
+  "x y z".  The flag without a standard face is refused by name: there is nothing to register onto.
+
+NOT built: the ``Vis`` animation dumps (:226-251) do not exist.  The reference's launcher for this class is not in its tree; DESIGN.md 4e-5 says where the defaults
 below come from."""
 import argparse
 import os
@@ -130,10 +133,22 @@ def content_loss(net, fls, aus, face_id, use_lip_weight=True, use_motion_loss=Fa
     return loss, fl_dis_pred
 
 
+def load_std_face(path):
+    """STD_FACE_LANDMARKS.txt: 68 rows "x y z" -> (204,) float32, the anchor of ``--use_reg_as_std``"""
+    std = np.loadtxt(path, dtype=np.float64)
+    if std.size != 204:
+        raise ValueError('%s: %d numbers, a standard face has 68 x 3' % (path, std.size))
+    return std.reshape(204).astype(np.float32)
+
+
 class ContentTrainer:
     def __init__(self, opt, device=None, dtype=torch.float32):
+        self.anchor = None
         if getattr(opt, 'use_reg_as_std', False):
-            raise NotImplementedError('--use_reg_as_std: the ICP registration of the identity frame is not built')
+            if not getattr(opt, 'std_face', None):
+                raise NotImplementedError('--use_reg_as_std without --std_face: the registration of the identity frame needs the '
+                                          'standard face to register onto')
+            self.anchor = load_std_face(opt.std_face)
         self.opt = opt
         self.device = torch.device(device if device is not None else ('cuda:0' if torch.cuda.is_available() else 'cpu'))
         self.dtype = dtype
@@ -174,6 +189,8 @@ class ContentTrainer:
                 close_fl = fl_ori[::10, 0, :]                                        # :171-173
                 idx = close_face_lip(close_fl.detach().cpu().numpy())
                 face_id = close_fl[idx:idx + 1, :]
+                if self.anchor is not None:                                          # :176-183
+                    face_id = self.registered_face_id(face_id)
                 for _ in range(self.opt.in_batch_nepoch):
                     start = 0
                     if is_training:                                                  # :189-192
@@ -193,6 +210,11 @@ class ContentTrainer:
             if epoch % self.opt.ckpt_epoch_freq == 0:
                 self.save('e_%d' % epoch, epoch)
         return mean
+
+    def registered_face_id(self, face_id):
+        """The (1, 204) identity frame registered onto the standard face: through float32 on the host, as the reference does."""
+        reg = module1.register_face(face_id.detach().cpu().numpy().astype(np.float32), self.anchor)
+        return torch.as_tensor(reg.reshape(1, 204), dtype=self.dtype, device=self.device)
 
     def save(self, save_type, epoch):
         os.makedirs(self.opt.ckpt_dir, exist_ok=True)
@@ -227,7 +249,9 @@ def make_parser():
     ap.add_argument('--drop_out', type=float, default=0.0)
     ap.add_argument('--use_prior_net', type=int, default=0)
     ap.add_argument('--ckpt_epoch_freq', type=int, default=1)
-    ap.add_argument('--use_reg_as_std', action='store_true', help='refused: the ICP registration is not built')
+    ap.add_argument('--use_reg_as_std', action='store_true',
+                    help='register every clip\'s identity frame onto the standard face (train_content.py:176-183); needs --std_face')
+    ap.add_argument('--std_face', default=None, help='STD_FACE_LANDMARKS.txt, 68 rows "x y z": the anchor of --use_reg_as_std')
     ap.add_argument('--au_mean_std', default=None, help='table of mel means and standard deviations to normalise with (default: none)')
     ap.add_argument('--seed', type=int, default=None, help='seed of the random segment starts')
     ap.add_argument('--device', default=None)
@@ -236,8 +260,9 @@ def make_parser():
 
 def main(argv=None):
     opt = make_parser().parse_args(argv)
-    if opt.use_reg_as_std:
-        raise SystemExit('module1_train: --use_reg_as_std is refused: the ICP registration of the identity frame is not built')
+    if opt.use_reg_as_std and not opt.std_face:
+        raise SystemExit('module1_train: --use_reg_as_std is refused without --std_face: the registration of the identity frame '
+                         'needs the standard face to register onto')
     # the switch is the process's: set for this run, put back behind it (a caller of ContentTrainer sets it itself)
     prev = module1.set_lstm_train_backend(opt.lstm) if opt.lstm else None
     try:

@@ -151,6 +151,32 @@ int32_t apq_image_landmarks_ok(const float* in, const float* out, const int32_t*
 int apq_image_landmarks(const float* in, float* out, const int32_t* stamps, int32_t n_stamps, int32_t T, double scale,
                         double shift_x, double shift_y, int32_t flags, void* stream);
 
+/* ------------------------------------------------------------------- rigid registration of landmark frames (seq_register.hip)
+ * Module1/util/icp.py on the 9-point "T shape" (points 27, 28, 29, 30, 33, 36, 39, 42, 45) of every frame, and its three uses
+ * (train_content.py:176-183, train_audio2landmark.py:312-338), as tests/register_reference.py states them in float64:
+ *   in [T][204] fp32, std [204] fp32  ->  out [T][204] fp32,  pose [T][12] fp64 or null
+ * Per frame, in this order:
+ *   APQ_REG_CENTER    p <- p - mean_68(p) + mean_68(std)
+ *   T = icp(frame's T shape, std's T shape): correspondences by index, at most 50 rounds of the best rigid fit (Kabsch through
+ *       a 3x3 SVD whose smallest direction is the one mirrored when the fit would reflect), stopped when the summed squared
+ *       distance moves by less than 1e-4 between rounds; then the fit of the frame's own T shape onto the moved one.
+ *       pose, when given, receives that frame's row-major 3x4 [R | t], before any angle is removed
+ *   APQ_REG_NO_X_ROT  with R = Rz(c) Ry(b) Rx(a): p <- Rz(c) Ry(b) (p - t) + t   (the reference's switch no_y_rotation)
+ *   APQ_REG_REGISTER  p <- R p + t   (excludes the two flags above)
+ * flags == 0 copies the rows (and still fills pose).  Rows are fp32 in and out, everything between is fp64, rounded once at the
+ * store.  One launch of T waves, a wave per frame: no workspace, no atomics, no host synchronisation; a frame's result does not
+ * depend on its place in the clip or on T.  A degenerate frame (T-shape covariance of rank below 2, NaN, |b| within 1e-6 of 90
+ * degrees) gets unspecified values in its own rows and nothing else.  out may be in itself (exactly in place), no other overlap
+ * of out or pose with in, std or each other.  1 <= T <= APQ_MAX_T; in, std, out 4-byte aligned (APQ_ALIGN_ELEM), pose 8-byte
+ * aligned (APQ_ALIGN_F64).  The `_ok` twin and the error codes follow the rules of the post-processing calls above.  Added
+ * without a change of APQ_ABI_VERSION: nothing that existed changed. */
+#define APQ_REG_CENTER 1
+#define APQ_REG_NO_X_ROT 2
+#define APQ_REG_REGISTER 4
+#define APQ_REG_MAX_ROUNDS 50   /* icp's max_iterations */
+int32_t apq_rigid_register_ok(const float* in, const float* std, const float* out, const double* pose, int32_t T, int32_t flags);
+int apq_rigid_register(const float* in, const float* std, float* out, double* pose, int32_t T, int32_t flags, void* stream);
+
 /* ------------------------------------------------------------------------------- the clip's f0 track (seq_f0.hip)
  * RAPT (Talkin 1995, the get_f0 defaults) with one NCCF pass at the full rate, as tests/f0_reference.py states it in float64:
  * apq_f0_candidates makes every frame's table (one workgroup per frame, no frame reads another's results), apq_f0_track runs
