@@ -1,4 +1,4 @@
-"""Module1's clip-level landmark post-processing on the device: the numpy / scipy functions of ``module1`` and
+"""Module1's clip-level landmark post-processing on the device: the numpy / scipy functions of ``landmark_host`` and
 ``stream.smooth_landmarks`` on CUDA tensors, through the ``apq_*`` post-processing calls of libapseq.so (csrc/seq/seq_post.hip).
 
 Every function takes device tensors and returns device tensors; none copies to the host, synchronises, or falls back: a call
@@ -9,7 +9,7 @@ import torch
 
 from . import _seqapi as Q
 from . import ops
-from .module1 import blink_stamps            # noqa: F401  (part of this module's surface)
+from .landmark_host import blink_stamps      # noqa: F401  (part of this module's surface)
 
 _TAPS = {}
 
@@ -74,7 +74,7 @@ def smooth_landmarks(fl):
 
 
 def calib_baseline(pred, amp_lip_x=2.0, amp_lip_y=2.0, ratio=0.5):
-    """``module1.calib_baseline`` on a (T, 204) tensor, 2 <= T <= 512."""
+    """``landmark_host.calib_baseline`` on a (T, 204) tensor, 2 <= T <= 512."""
     x = _dev32(pred, 'calib_baseline', Q.LM_C)
     y = torch.empty_like(x)
     Q.check(Q.lib().apq_calib_baseline(ops._ptr(x), ops._ptr(y), x.shape[0], int(x.shape[0] * ratio), float(amp_lip_x),
@@ -101,12 +101,12 @@ def segment_assemble(fl, base=None, fid=None, ratio=0.99, amp=1.0, close=True, l
 
 
 def close_pose_branch_mouth(fl, ratio=0.99):
-    """``module1.close_pose_branch_mouth`` on a (T, 204) tensor (out of place)."""
+    """``landmark_host.close_pose_branch_mouth`` on a (T, 204) tensor (out of place)."""
     return segment_assemble(fl, ratio=ratio, close=True, lip=False)
 
 
 def solve_inverse_lip(fl):
-    """``module1.solve_inverse_lip`` on a (T, 204) tensor (out of place)."""
+    """``landmark_host.solve_inverse_lip`` on a (T, 204) tensor (out of place)."""
     return segment_assemble(fl, close=False, lip=True)
 
 
@@ -115,7 +115,7 @@ def rigid_register(fl, std, center=False, no_x_rot=False, register=False, pose=F
     ``module1.stabilise_head`` with ``center`` (centerize_face) and ``no_x_rot`` (the reference's no_y_rotation), or
     ``module1.register_face`` on every frame with ``register`` (which excludes the other two).  ``out``: a contiguous (T, 204)
     tensor to write into, ``fl`` itself for in place.  With ``pose`` also returns the (T, 3, 4) float64 [R | t] that
-    ``module1.icp_t_shape`` gives for every frame (after the centring, before any angle is removed)."""
+    ``landmark_host.icp_t_shape`` gives for every frame (after the centring, before any angle is removed)."""
     x = _dev32(fl, 'rigid_register', Q.LM_C)
     sd = _dev32(std.reshape(1, -1) if torch.is_tensor(std) else std, 'rigid_register', Q.LM_C)
     if out is None:
@@ -147,7 +147,7 @@ def image_landmarks(fl, scale=1.0, shift=(0.0, 0.0), transform=True, stamps=None
 
 
 def add_naive_eye(fl, rng=np.random):
-    """``module1.add_naive_eye`` on a (T, 68, 3) tensor (out of place); T >= 46, else ValueError before anything is launched."""
+    """``landmark_host.add_naive_eye`` on a (T, 68, 3) tensor (out of place); T >= 46, else ValueError before anything is launched."""
     fl = _dev32(fl, 'add_naive_eye')
     if fl.dim() != 3 or fl.shape[1:] != (68, 3):
         raise ValueError('landmark_post.add_naive_eye takes (T, 68, 3), not %s' % (tuple(fl.shape),))

@@ -1,26 +1,28 @@
-"""Module1's audio -> landmark networks and clip-level landmark pipeline.
+"""Module1's audio -> landmark networks and the clip driver above them.
 
-Mirrors of the reference's two networks, attribute for attribute, so that its checkpoints load with ``strict=True``:
+What this file holds:
 
-* ``Audio2LandmarkContent`` = ``Audio2landmark_content`` (Module1/src/models/model_audio2landmark.py:28-90; checkpoint
-  ``ckpt_content_branch.pth['model_g_face_id']``, train_audio2landmark.py:71-79): a 3-layer LSTM over 18-frame mel
-  windows (behind the ``fc_prior`` MLP when ``use_prior_net``) + a 3-layer MLP, ~1.5 M parameters;
-* ``Audio2LandmarkPos`` = ``Audio2landmark_pos`` (:296-386; checkpoint ``ckpt_speaker_branch.pth['G']``,
-  train_audio2landmark.py:55-66): LSTM audio encoder, speaker-embedding MLP, a 2-layer / 2-head self-attention encoder
-  (``Embedder`` / ``PositionalEncoder`` / ``EncoderLayer`` / ``Norm``, :94-262) over the windows of a segment, output
-  MLP.  The reference also constructs a ``Decoder`` it never runs; it is built here too because its tensors are in the
-  checkpoint.
+* the reference's two networks, attribute for attribute, so that its checkpoints load with ``strict=True``:
+  ``Audio2LandmarkContent`` = ``Audio2landmark_content`` (Module1/src/models/model_audio2landmark.py:28-90; a 3-layer LSTM over
+  18-frame mel windows, behind the ``fc_prior`` MLP when ``use_prior_net``, + a 3-layer MLP) and ``Audio2LandmarkPos`` =
+  ``Audio2landmark_pos`` (:296-386; LSTM audio encoder, speaker-embedding MLP, a 2-layer / 2-head self-attention encoder, :94-262,
+  output MLP; its never-run ``Decoder`` is built too because its tensors are in the checkpoint);
+* the clip drivers: ``predict_landmarks_speaker_aware`` = ``Audio2landmark_model.test`` (train_audio2landmark.py:247-338) and
+  ``predict_landmarks``, the content branch alone; ``to_image_landmarks``, ``register_face`` and ``stabilise_head``, which send a CUDA
+  tensor to ``landmark_post`` (libapseq.so) and everything else to ``landmark_host`` (the reference's numpy / scipy statements);
+* ``load_module1`` and the photo's face normalisation.  Training the content branch is module1_train.py.
 
-Both run ONCE per clip over all windows: stock PyTorch-ROCm by default; ``set_lstm_backend('hip')`` (or
-APAMD_MODULE1_LSTM=hip) moves their LSTMs to the batched kernel of libapseq.so.  ``predict_landmarks_speaker_aware`` is ``Audio2landmark_model.test`` (train_audio2landmark.py:101-141,
-235-245, 247-309, 594-617) followed by the clip-level post-processing of main_end2end_module2.py:262-272; the simpler
-``predict_landmarks`` is the content branch alone (``__train_face_wo_pos__``).  That post-processing is numpy / scipy on the host
-by default; ``set_post_backend('device')`` (or APAMD_MODULE1_POST=device) runs it in libapseq.so (landmark_post.py) and keeps the
-landmark sequence on the GPU.  ``set_encoder_backend('hip')`` (or APAMD_MODULE1_ENCODER=hip) runs the pose network's self-attention
-encoder as two launches per layer of libapseq.so (encoder_hip.py).  Training the content branch is module1_train.py; ``set_lstm_train_backend('hip')`` (or
-APAMD_MODULE1_LSTM_TRAIN=hip) puts its LSTM on the training kernel pair of libapseq.so.  NOT built: the AutoVC mel / speaker
-embedding front end (librosa / pysptk / pyworld / resemblyzer are not in this image, and neither are the checkpoints);
-callers pass the (T, 18, 80) mel windows and the 256-d speaker embedding the reference's ``au_data`` / ``au_emb`` hold.
+The four switches (``set_X_backend(name)`` returns the previous name, ``get_X_backend()``; the variable is read at import; an unknown
+name is a ``ValueError``).  The first choice is the default, and what the last column names always runs on it:
+
+  X           variable                  choices          never served by the kernels
+  lstm        APAMD_MODULE1_LSTM        library | hip    CPU tensors, training mode, autograd (nn.LSTM; hip: lstm_hip.py)
+  lstm_train  APAMD_MODULE1_LSTM_TRAIN  library | hip    anything but the content branch in training with gradients
+  encoder     APAMD_MODULE1_ENCODER     library | hip    CPU tensors, a mask, training with gradients (hip: encoder_hip.py)
+  post        APAMD_MODULE1_POST        host | device    CPU tensors and CPU networks (device: the sequence stays a CUDA tensor)
+
+NOT built: the reference's librosa / pysptk / pyworld / resemblyzer front end; callers pass the (T, 18, 80) mel windows and the
+256-d speaker embedding its ``au_data`` / ``au_emb`` hold.
 """
 import copy
 import math
@@ -31,113 +33,57 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .stream import smooth_landmarks
+from . import landmark_host, landmark_post
 
 FACE_ID_FEAT_SIZE = 204       # 68 x 3, model_audio2landmark.py:23
 
-# Who runs the two 3-layer LSTMs at inference on the device: 'library' = nn.LSTM (MIOpen), 'hip' = one apq_lstm_layer_fwd
-# launch per layer (lstm_hip.lstm_forward_batched, libapseq.so).  CPU tensors, training mode and autograd always take nn.LSTM.
 LSTM_BACKENDS = ('library', 'hip')
-
-
-def _checked_backend(name):
-    if name not in LSTM_BACKENDS:
-        raise ValueError('Module1 LSTM backend %r (known: %s)' % (name, ', '.join(LSTM_BACKENDS)))
-    return name
-
-
-_lstm_backend = _checked_backend(os.environ.get('APAMD_MODULE1_LSTM') or 'library')
-
-
-def set_lstm_backend(name):
-    """Select the LSTM backend of both landmark networks; returns the previous one."""
-    global _lstm_backend
-    prev, _lstm_backend = _lstm_backend, _checked_backend(name)
-    return prev
-
-
-def get_lstm_backend():
-    return _lstm_backend
-
-
-# Who runs the clip-level post-processing between the networks and the frame loop: 'host' = numpy / scipy below (the
-# reference's own statements), 'device' = the apq_* calls of libapseq.so (landmark_post.py): the sequence then stays a CUDA
-# tensor from the mel windows on.  CPU tensors and CPU networks always take the host functions.
 POST_BACKENDS = ('host', 'device')
-
-
-def _checked_post_backend(name):
-    if name not in POST_BACKENDS:
-        raise ValueError('Module1 post-processing backend %r (known: %s)' % (name, ', '.join(POST_BACKENDS)))
-    return name
-
-
-_post_backend = _checked_post_backend(os.environ.get('APAMD_MODULE1_POST') or 'host')
-
-
-def set_post_backend(name):
-    """Select where the landmark post-processing runs; returns the previous backend."""
-    global _post_backend
-    prev, _post_backend = _post_backend, _checked_post_backend(name)
-    return prev
-
-
-def get_post_backend():
-    return _post_backend
-
-
-# Who runs the content branch's LSTM when it is TRAINED (module in training mode, gradients enabled): 'library' = nn.LSTM,
-# 'hip' = one apq_lstm_layer_fwd_train / apq_lstm_layer_bwd launch pair per layer (lstm_hip.lstm_train_batched).  Separate from
-# the inference switch above, which it leaves alone.
-_lstm_train_backend = _checked_backend(os.environ.get('APAMD_MODULE1_LSTM_TRAIN') or 'library')
-
-
-def set_lstm_train_backend(name):
-    """Select the LSTM backend of ``Audio2LandmarkContent`` in training; returns the previous one."""
-    global _lstm_train_backend
-    prev, _lstm_train_backend = _lstm_train_backend, _checked_backend(name)
-    return prev
-
-
-def get_lstm_train_backend():
-    return _lstm_train_backend
-
-
-# Who runs the pose network's self-attention encoder at inference on the device: 'library' = the torch modules below, 'hip' = two
-# launches per layer of libapseq.so (encoder_hip.encoder_forward: apq_enc_qkv, apq_enc_attn_ff).  CPU tensors, a mask and training
-# with gradients always take the torch modules.
 ENCODER_BACKENDS = ('library', 'hip')
 
 
-def _checked_encoder_backend(name):
-    if name not in ENCODER_BACKENDS:
-        raise ValueError('Module1 encoder backend %r (known: %s)' % (name, ', '.join(ENCODER_BACKENDS)))
-    return name
+class _Switch:
+    """One backend choice: ``what`` names it in messages, ``env`` is read once, here; ``value`` is the current choice."""
+
+    def __init__(self, what, env, choices, default):
+        self.what, self.choices = what, choices
+        self.value = self.checked(os.environ.get(env) or default)
+
+    def checked(self, name):
+        if name not in self.choices:
+            raise ValueError('Module1 %s backend %r (known: %s)' % (self.what, name, ', '.join(self.choices)))
+        return name
+
+    def set(self, name):
+        """Select ``name`` (the module docstring's table says what for); returns the previous choice.  An unknown name raises
+        ``ValueError`` and leaves the choice as it was."""
+        prev, self.value = self.value, self.checked(name)
+        return prev
+
+    def get(self):
+        """The current choice."""
+        return self.value
 
 
-_encoder_backend = _checked_encoder_backend(os.environ.get('APAMD_MODULE1_ENCODER') or 'library')
-
-
-def set_encoder_backend(name):
-    """Select who runs ``Encoder.forward`` at inference; returns the previous backend."""
-    global _encoder_backend
-    prev, _encoder_backend = _encoder_backend, _checked_encoder_backend(name)
-    return prev
-
-
-def get_encoder_backend():
-    return _encoder_backend
+_lstm = _Switch('LSTM', 'APAMD_MODULE1_LSTM', LSTM_BACKENDS, 'library')
+_lstm_train = _Switch('LSTM', 'APAMD_MODULE1_LSTM_TRAIN', LSTM_BACKENDS, 'library')
+_encoder = _Switch('encoder', 'APAMD_MODULE1_ENCODER', ENCODER_BACKENDS, 'library')
+_post = _Switch('post-processing', 'APAMD_MODULE1_POST', POST_BACKENDS, 'host')
+set_lstm_backend, get_lstm_backend = _lstm.set, _lstm.get
+set_lstm_train_backend, get_lstm_train_backend = _lstm_train.set, _lstm_train.get
+set_encoder_backend, get_encoder_backend = _encoder.set, _encoder.get
+set_post_backend, get_post_backend = _post.set, _post.get
 
 
 def _lstm_last(lstm, x, trainable=False):
     """``lstm(x)[0][:, -1, :]``, the one thing both networks read from their LSTM.  ``trainable``: the caller takes part in the
     training switch (the content branch)."""
     if trainable and lstm.training and torch.is_grad_enabled():
-        if _lstm_train_backend == 'hip':
+        if _lstm_train.value == 'hip':
             from . import lstm_hip
             return lstm_hip.lstm_train_batched(lstm, x, last_only=True)
         return lstm(x)[0][:, -1, :]
-    if _lstm_backend == 'hip':
+    if _lstm.value == 'hip':
         from . import lstm_hip
         return lstm_hip.lstm_forward_batched(lstm, x, last_only=True)
     return lstm(x)[0][:, -1, :]
@@ -285,7 +231,7 @@ class _Stack(nn.Module):                                                        
 def _encoder_on_kernels(encoder, x, mask):
     """Does ``Encoder.forward`` take the kernels of libapseq.so?  Only with the 'hip' backend, a CUDA tensor, no mask, gradients
     disabled or the module in eval mode, and shapes the library serves (encoder_hip.supported: its host-only ``_ok`` calls)."""
-    if not (_encoder_backend == 'hip' and x.is_cuda and mask is None and not (torch.is_grad_enabled() and encoder.training)):
+    if not (_encoder.value == 'hip' and x.is_cuda and mask is None and not (torch.is_grad_enabled() and encoder.training)):
         return False
     from . import encoder_hip
     return encoder_hip.supported(encoder, x)
@@ -342,166 +288,26 @@ class Audio2LandmarkPos(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------- clip-level pipeline
-def _savgol(x, window, order=3):
-    from scipy.signal import savgol_filter
-    return savgol_filter(x, window, order, axis=0)
-
-
-def close_pose_branch_mouth(fl, ratio=0.99):
-    """train_audio2landmark.py:119-130 on (T, 204): pull the upper / lower lip contours of the pose branch together."""
-    fl = fl.reshape((-1, 68, 3))
-    index1, index2 = list(range(59, 54, -1)), list(range(67, 64, -1))
-    mean_out = 0.5 * fl[:, 49:54] + 0.5 * fl[:, index1]
-    fl[:, 49:54] = mean_out * ratio + fl[:, 49:54] * (1 - ratio)
-    fl[:, index1] = mean_out * ratio + fl[:, index1] * (1 - ratio)
-    mean_in = 0.5 * (fl[:, 61:64] + fl[:, index2])
-    fl[:, 61:64] = mean_in * ratio + fl[:, 61:64] * (1 - ratio)
-    fl[:, index2] = mean_in * ratio + fl[:, index2] * (1 - ratio)
-    return fl.reshape(-1, 204)
-
-
-def calib_baseline(pred, amp_lip_x=2.0, amp_lip_y=2.0, ratio=0.5):
-    """__calib_baseline_pred_fls__ (:235-245): per coordinate, subtract the mean of its K smallest values over the
-    segment, then amplify the mouth's x / y."""
-    x = np.array(pred, dtype=np.float32, copy=True)
-    k = int(x.shape[0] * ratio)
-    for c in range(204):
-        idx = np.argpartition(x[:, c], k)
-        x[:, c] = x[:, c] - np.mean(x[idx[:k], c])
-    x[:, 48 * 3::3] *= amp_lip_x
-    x[:, 48 * 3 + 1::3] *= amp_lip_y
-    return x
-
-
-def _signed_area(pts):
-    """util/geo_math.py:27-39: fan of signed triangles from the first vertex"""
-    ab, ac = pts[1:-1] - pts[0], pts[2:] - pts[0]
-    return float(0.5 * np.sum(ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]))
-
-
-def solve_inverse_lip(fl):
-    """__solve_inverse_lip2__ (:594-617) on (T, 204), frame by frame (frame j reads the already fixed frame j - 1)."""
-    for j in range(fl.shape[0]):
-        if _signed_area(fl[j].reshape(68, 3)[60:68, 0:2]) < 0:
-            for a, b in ((63, 65), (62, 66), (61, 67)):
-                fl[j, b * 3:b * 3 + 3] = 0.5 * (fl[j, a * 3:a * 3 + 3] + fl[j, b * 3:b * 3 + 3])
-                fl[j, a * 3:a * 3 + 3] = fl[j, b * 3:b * 3 + 3]
-            p = max(j - 1, 0)
-            for dst, src in (((55, 59), (64, 68)), ((59, 60), (60, 61)), ((49, 54), (60, 65))):
-                d = slice(dst[0] * 3 + 1, dst[1] * 3 + 1, 3)
-                s = slice(src[0] * 3 + 1, src[1] * 3 + 1, 3)
-                fl[j, d] = fl[j, s] + fl[p, d] - fl[p, s]
-    return fl
-
-
-def blink_stamps(length, rng=np.random):
-    """The frames ``add_naive_eye`` blinks at in a clip of ``length`` frames (util/utils.py:373-380): 30, then steps of
-    60 + randint(30, 90) while they leave 16 frames behind them.  Draws from ``rng`` what the reference's loop draws."""
-    k2 = 15
-    stamps, t = [30], 30
-    while t < length - 1 - k2:
-        t += 60
-        t += rng.randint(30, 90)
-        if t < length - 1 - k2:
-            stamps.append(t)
-    return stamps
-
-
-def add_naive_eye(fl, rng=np.random):
-    """util/utils.py:361-393 on (T, 68, C): eyelids slightly closed throughout, plus blinks at random times (the
-    reference draws them from numpy's global generator)."""
-    pairs = ((37, 41), (38, 40), (43, 47), (44, 46))
-    r = 0.95
-    for a, b in pairs:
-        fa, fb = fl[:, a].copy(), fl[:, b].copy()
-        fl[:, a], fl[:, b] = r * fa + (1 - r) * fb, (1 - r) * fa + r * fb
-    k1, k2 = 10, 15
-    stamps = blink_stamps(fl.shape[0], rng)
-    lids = [37, 38, 40, 41, 43, 44, 46, 47]
-    for t in stamps:
-        for a, b in pairs:
-            v = 0.25 * fl[t, a] + 0.75 * fl[t, b]
-            fl[t, a], fl[t, b] = v, v.copy()
-        for t0 in range(t - k1 + 1, t):
-            w = (t - t0) / 1. / k1
-            fl[t0, lids] = w * fl[t - k1, lids] + (1 - w) * fl[t, lids]
-        for t0 in range(t + 1, t + k2):
-            w = (t + k2 - 1 - t0) / 1. / k2
-            fl[t0, lids] = w * fl[t, lids] + (1 - w) * fl[t + k2, lids]
-    return fl
-
-
-# ------------------------------------------------------------------------------------------------- rigid registration
-T_SHAPE_IDX = (27, 28, 29, 30, 33, 36, 39, 42, 45)      # nose bridge, nose base, the four eye corners: the face's rigid part
-
-
-def _best_fit_transform(a, b):
-    """util/icp.py:5-55: the rigid map (R, t) of the points a (N, 3) onto b (N, 3), Kabsch through LAPACK's SVD; when the fit
-    would reflect, the direction of the smallest singular value is mirrored."""
-    ca, cb = a.mean(axis=0), b.mean(axis=0)
-    u, _, vt = np.linalg.svd((a - ca).T @ (b - cb))
-    r = vt.T @ u.T
-    if np.linalg.det(r) < 0:
-        vt[-1] *= -1
-        r = vt.T @ u.T
-    return r, cb - r @ ca
-
-
-def icp_t_shape(frame, std, max_iterations=50, tolerance=1e-4):
-    """``icp(frame[T shape], std[T shape])`` of util/icp.py:77-132, whose neighbour search is commented out: the points
-    correspond by index.  frame, std: 68 x 3 in any shape.  Returns the (3, 4) float64 [R | t] that maps frame onto std."""
-    idx = list(T_SHAPE_IDX)
-    a = np.asarray(frame, dtype=np.float64).reshape(68, 3)[idx]
-    b = np.asarray(std, dtype=np.float64).reshape(68, 3)[idx]
-    src, prev = a.copy(), 0.0
-    for _ in range(max_iterations):
-        err = np.sum((src - b) ** 2)
-        r, t = _best_fit_transform(src, b)
-        src = src @ r.T + t
-        if abs(prev - err) < tolerance:
-            break
-        prev = err
-    r, t = _best_fit_transform(a, src)
-    return np.hstack((r, t[:, None]))
-
-
 def register_face(frame, anchor):
     """train_content.py:176-183 (``--use_reg_as_std``): the frame's 68 points moved by ``icp_t_shape(frame, anchor)``.
     Rows are float32 in and out, float64 between.  Returns (204,) float32; a CUDA tensor goes through libapseq.so."""
     if torch.is_tensor(frame) and frame.is_cuda:
-        from . import landmark_post as lp
-        return lp.rigid_register(frame.float().reshape(1, -1), torch.as_tensor(anchor, dtype=torch.float32, device=frame.device),
-                                 register=True).view(-1)
-    p = np.asarray(frame, dtype=np.float32).astype(np.float64).reshape(68, 3)
-    t34 = icp_t_shape(p, np.asarray(anchor, dtype=np.float32))
-    return (p @ t34[:, :3].T + t34[:, 3]).reshape(204).astype(np.float32)
+        anchor = torch.as_tensor(anchor, dtype=torch.float32, device=frame.device)
+        return landmark_post.rigid_register(frame.float().reshape(1, -1), anchor, register=True).view(-1)
+    return landmark_host.register_face(frame, anchor)
 
 
 def stabilise_head(fl, std, centerize_face=False, no_y_rotation=False):
-    """The two head-stabilisation switches of the reference's test pass (train_audio2landmark.py:312-338) on (T, 204) landmarks,
-    in its order: ``centerize_face`` moves every frame's 68-point mean onto that of ``std``; ``no_y_rotation`` registers every
-    frame's T shape onto ``std``'s and, with the fitted rotation R = Rz(c) Ry(b) Rx(a) and translation t, maps every point to
-    Rz(c) Ry(b) (p - t) + t -- the angle set to zero is the first of scipy's extrinsic 'xyz' triple, whatever the switch's name
-    says.  Rows are float32 in and out, float64 between.  numpy in, numpy out; a CUDA tensor is served by one launch of
+    """The two head-stabilisation switches of the reference's test pass (train_audio2landmark.py:312-338) on (T, 204) landmarks
+    (``landmark_host.stabilise_head`` says what they do).  numpy in, numpy out; a CUDA tensor is served by one launch of
     libapseq.so (landmark_post.rigid_register) and stays on the device.  With both switches off ``fl`` is returned as it is."""
     if not (centerize_face or no_y_rotation):
         return fl
     if torch.is_tensor(fl) and fl.is_cuda:
-        from . import landmark_post as lp
         std = torch.as_tensor(std, dtype=torch.float32, device=fl.device).reshape(-1)
-        return lp.rigid_register(fl.float().reshape(-1, FACE_ID_FEAT_SIZE), std, center=centerize_face, no_x_rot=no_y_rotation)
-    from scipy.spatial.transform import Rotation
-    x = np.asarray(fl, dtype=np.float32).astype(np.float64).reshape(-1, 68, 3)
-    sd = np.asarray(std.detach().cpu() if torch.is_tensor(std) else std, dtype=np.float32).astype(np.float64).reshape(68, 3)
-    if centerize_face:
-        x = x - x.mean(axis=1, keepdims=True) + sd.mean(axis=0)
-    if no_y_rotation:
-        for i in range(x.shape[0]):
-            t34 = icp_t_shape(x[i], sd)
-            t = t34[:, 3]
-            _, b, c = Rotation.from_matrix(t34[:, :3]).as_euler('xyz')
-            x[i] = (x[i] - t) @ Rotation.from_euler('xyz', [0.0, b, c]).as_matrix().T + t
-    return x.reshape(-1, FACE_ID_FEAT_SIZE).astype(np.float32)
+        return landmark_post.rigid_register(fl.float().reshape(-1, FACE_ID_FEAT_SIZE), std, center=centerize_face,
+                                            no_x_rot=no_y_rotation)
+    return landmark_host.stabilise_head(fl, std.detach().cpu() if torch.is_tensor(std) else std, centerize_face, no_y_rotation)
 
 
 @torch.no_grad()
@@ -511,75 +317,47 @@ def predict_landmarks_speaker_aware(net_g, net_c, au_windows, spk_emb, face_id, 
     """``Audio2landmark_model.test`` (train_audio2landmark.py:247-309 with __train_face_and_pos__ :101-141):
     au_windows (T, 18, 80), spk_emb (256,), face_id (204,) -> (T, 204) landmarks in Module1's normalised frame.
     Per 512-window segment: pose branch G (speaker embedding x 3, z = 0) -> Savitzky-Golay over the segment -> lips
-    pulled together -> x amp_pos; content branch C on the first 18 frames -> calibrated; sum + face id; inverted-lip fix.
-    Then the nose-top extrapolation and a (5, 3) Savitzky-Golay over the clip, and behind it ``stabilise_head`` against ``face_id``
+    pulled together -> x amp_pos; content branch C on the first 18 frames -> calibrated; sum + face id; inverted-lip fix; the
+    nose-top extrapolation.  Then a (5, 3) Savitzky-Golay over the clip, and behind it ``stabilise_head`` against ``face_id``
     when ``centerize_face`` or ``no_y_rotation`` is set (:312-338; off, as in the reference's readme, nothing more runs).
-    With the 'device' post-processing backend and networks on the GPU the result is a (T, 204) CUDA tensor and nothing between
-    the windows and it touches the host; otherwise a numpy array."""
+    With the 'device' post-processing backend and networks on the GPU every step behind the networks is a launch of libapseq.so
+    (landmark_post), the result is a (T, 204) CUDA tensor and nothing between the windows and it touches the host; otherwise the
+    steps are landmark_host's and the result a numpy array.  A segment of fewer than 10 windows is dropped (:288-289)."""
     net_g.eval()
     net_c.eval()
     dev = next(net_g.parameters()).device
     au = torch.as_tensor(au_windows, dtype=torch.float32, device=dev)
     emb = torch.as_tensor(spk_emb, dtype=torch.float32, device=dev).view(1, -1).expand(au.shape[0], -1)
     fid = torch.as_tensor(face_id, dtype=torch.float32, device=dev).view(1, FACE_ID_FEAT_SIZE)
-    if _post_backend == 'device' and dev.type == 'cuda':
-        fl = _speaker_aware_on_device(net_g, net_c, au, emb, fid, amp_pos, amp_lip_x, amp_lip_y, segment, smooth_win,
-                                      close_mouth_ratio)
-        return stabilise_head(fl, fid.view(-1), centerize_face, no_y_rotation)
-    out = []
-    for j in range(0, au.shape[0], segment):
-        a, e = au[j:j + segment], emb[j:j + segment]
-        if a.shape[0] < 10:                                                      # :288-289
-            continue
-        z = torch.zeros(a.shape[0], 128, device=dev)
-        dis = net_g(a, e * 3.0, fid.repeat(a.shape[0], 1), None, z)[0].cpu().numpy()
-        dis = _savgol(dis, int(min(dis.shape[0] - 1, smooth_win) // 2 * 2 + 1))
-        dis = close_pose_branch_mouth(dis, close_mouth_ratio).astype(np.float32) * np.float32(amp_pos)
-        base = net_c(a[:, 0:18, :], fid)[0].cpu().numpy()
-        seg = dis + calib_baseline(base, amp_lip_x, amp_lip_y) + fid.cpu().numpy()
-        out.append(solve_inverse_lip(seg))
-    fl = np.concatenate(out)
-    fl[:, 27 * 3:28 * 3] = fl[:, 28 * 3:29 * 3] * 2 - fl[:, 29 * 3:30 * 3]       # revise the nose top point (:300)
-    return stabilise_head(_savgol(fl, 5), fid.cpu().numpy().reshape(-1), centerize_face, no_y_rotation)
-
-
-def _speaker_aware_on_device(net_g, net_c, au, emb, fid, amp_pos, amp_lip_x, amp_lip_y, segment, smooth_win, close_mouth_ratio):
-    """The loop of ``predict_landmarks_speaker_aware`` with every step behind the networks in libapseq.so: per segment one
-    Savitzky-Golay, one calibration and one assembly launch (lips closed, sum, inverted-lip fix, nose top) that writes the
-    segment's rows of the clip; then the clip's Savitzky-Golay.  Which segments are kept is known from the shapes."""
-    from . import landmark_post as lp
-    dev = au.device
-    lens = [min(segment, au.shape[0] - j) for j in range(0, au.shape[0], segment)]
-    fl = torch.empty((sum(n for n in lens if n >= 10), FACE_ID_FEAT_SIZE), dtype=torch.float32, device=dev)
-    if fl.shape[0] == 0:
+    on_device = _post.value == 'device' and dev.type == 'cuda'
+    post = landmark_post if on_device else landmark_host
+    take = (lambda t: t) if on_device else (lambda t: t.cpu().numpy())           # what the post-processing module is handed
+    lens = [min(segment, au.shape[0] - j) for j in range(0, au.shape[0], segment)]       # kept segments: known from the shapes
+    kept = sum(n for n in lens if n >= 10)
+    if kept == 0:
         raise ValueError('predict_landmarks_speaker_aware: no segment of at least 10 windows')
-    row = 0
+    fl = (torch.empty((kept, FACE_ID_FEAT_SIZE), dtype=torch.float32, device=dev) if on_device
+          else np.empty((kept, FACE_ID_FEAT_SIZE), dtype=np.float32))
+    fid_p, row = take(fid), 0
     for k, n in enumerate(lens):
-        if n < 10:                                                               # :288-289
+        if n < 10:
             continue
         a, e = au[k * segment:k * segment + n], emb[k * segment:k * segment + n]
         z = torch.zeros(n, 128, device=dev)
-        dis = net_g(a, e * 3.0, fid.repeat(n, 1), None, z)[0]
-        dis = lp.savgol(dis, int(min(n - 1, smooth_win) // 2 * 2 + 1))
-        base = lp.calib_baseline(net_c(a[:, 0:18, :], fid)[0], amp_lip_x, amp_lip_y)
-        lp.segment_assemble(dis, base, fid, close_mouth_ratio, amp_pos, close=True, lip=True, nose=True, out=fl[row:row + n])
+        dis = post.savgol(take(net_g(a, e * 3.0, fid.repeat(n, 1), None, z)[0]), int(min(n - 1, smooth_win) // 2 * 2 + 1))
+        base = post.calib_baseline(take(net_c(a[:, 0:18, :], fid)[0]), amp_lip_x, amp_lip_y)
+        post.segment_assemble(dis, base, fid_p, close_mouth_ratio, amp_pos, close=True, lip=True, nose=True, out=fl[row:row + n])
         row += n
-    return lp.savgol(fl, 5)
+    return stabilise_head(post.savgol(fl, 5), fid_p.reshape(-1), centerize_face, no_y_rotation)
 
 
 def to_image_landmarks(fl, scale=1.0, shift=(0.0, 0.0), eyes=True, smooth=True, rng=np.random):
     """main_end2end_module2.py:262-272 on the (T, 204) output above: flip / scale / shift x and y into image pixels,
     ``add_naive_eye``, the two clip-level Savitzky-Golay filters.  Returns (T, 68, 3): a numpy array, or for a CUDA tensor a
-    CUDA tensor made by two launches of libapseq.so (the blink frames are drawn from ``rng`` on the host, as here)."""
+    CUDA tensor made by two launches of libapseq.so (the blink frames are drawn from ``rng`` on the host, as there)."""
     if torch.is_tensor(fl) and fl.is_cuda:
-        from . import landmark_post as lp
-        return lp.to_image_landmarks(fl.float(), scale, shift, eyes, smooth, rng)
-    fl = np.array(fl, dtype=np.float64).reshape((-1, 68, 3))
-    fl[:, :, 0:2] = -fl[:, :, 0:2]
-    fl[:, :, 0:2] = fl[:, :, 0:2] / scale - np.asarray(shift, dtype=np.float64)
-    if eyes:
-        fl = add_naive_eye(fl, rng)
-    return smooth_landmarks(fl) if smooth else fl.astype(np.float32)
+        return landmark_post.to_image_landmarks(fl.float(), scale, shift, eyes, smooth, rng)
+    return landmark_host.to_image_landmarks(fl, scale, shift, eyes, smooth, rng)
 
 
 @torch.no_grad()
@@ -597,7 +375,7 @@ def predict_landmarks(net, au_windows, face_id, scale=1.0, shift=(0.0, 0.0), seg
         dis, f = net(au[j:j + segment][:, 0:18, :], fid)
         outs.append(dis + f)
     fl = torch.cat(outs, 0)
-    if not (_post_backend == 'device' and fl.is_cuda):
+    if not (_post.value == 'device' and fl.is_cuda):
         fl = fl.cpu().numpy()
     return to_image_landmarks(fl, scale, shift, eyes=False, smooth=smooth)[:, :, :2]
 

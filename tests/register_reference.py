@@ -1,6 +1,6 @@
 """The float64 statement of the rigid landmark registration (Module1/util/icp.py and its uses in train_content.py:176-183 and
 train_audio2landmark.py:312-338), in numpy only.  apq_rigid_register (csrc/seq/seq_register.hip) and the numpy twins of
-``animateportrait_amd.module1`` are pinned to it; tests/golden/register.npz pins it to the reference's own functions.
+``animateportrait_amd.landmark_host`` are pinned to it; tests/golden/register.npz pins it to the reference's own functions.
 
 Arithmetic contract: rows are float32 in and out, everything between is float64, one rounding to float32 at the end.
 

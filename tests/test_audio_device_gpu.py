@@ -310,7 +310,7 @@ def test_end2end_stage_with_the_device_front_end(dev, golden, tmp_path, monkeypa
         return real_read(path)
     monkeypatch.setattr(m1, 'predict_landmarks_speaker_aware', spy)
     monkeypatch.setattr(audio, 'read_wav', counted)
-    before = m1._post_backend
+    before = m1.get_post_backend()
     try:
         np.random.seed(0)
         a = end2end.make_parser().parse_known_args(base + ['--audio_frontend', 'device'])[0]

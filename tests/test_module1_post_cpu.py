@@ -127,14 +127,14 @@ def test_the_bindings_constants_are_the_headers():
 def test_blink_stamps_are_the_host_functions(T, seed):
     """The host add_naive_eye on a ramp: the two lids of a pair coincide exactly at the blink frames and nowhere else (the
     frames around a blink are blends with a weight > 0 on an open frame)."""
-    from animateportrait_amd import module1 as m1, landmark_post as lp
+    from animateportrait_amd import landmark_host as lh, landmark_post as lp
     t, p, c = np.meshgrid(np.arange(T), np.arange(68), np.arange(3), indexing='ij')
     ramp = 0.01 * t + 1.0 * p + 0.1 * c
     r_host, r_fn = np.random.RandomState(seed), np.random.RandomState(seed)
-    out = m1.add_naive_eye(ramp.copy(), r_host)
+    out = lh.add_naive_eye(ramp.copy(), r_host)
     seen = [f for f in range(T) if all(np.array_equal(out[f, a], out[f, b]) for a, b in ((37, 41), (38, 40), (43, 47), (44, 46)))]
     stamps = lp.blink_stamps(T, r_fn)
-    assert lp.blink_stamps is m1.blink_stamps
+    assert lp.blink_stamps is lh.blink_stamps
     assert stamps == seen and stamps[0] == 30
     assert all(b - a >= 90 for a, b in zip(stamps, stamps[1:])) and all(s < T - 16 for s in stamps[1:]) and stamps[-1] + 15 <= T - 1
     assert len(stamps) == {46: 1, 200: 2}.get(T, len(stamps)) and (T != 625 or len(stamps) >= 4)

@@ -1,5 +1,5 @@
 """GPU (-m gpu): Module1's clip-level landmark post-processing on the device (landmark_post.py over the apq_* calls of
-libapseq.so, csrc/seq/seq_post.hip) against the host functions it restates -- scipy's savgol_filter, module1.calib_baseline,
+libapseq.so, csrc/seq/seq_post.hip) against the host functions it restates -- scipy's savgol_filter, landmark_host.calib_baseline,
 close_pose_branch_mouth / solve_inverse_lip, add_naive_eye, stream.smooth_landmarks -- then the whole stage against the
 reference-made golden (tests/golden/module1.npz) and the frame loop fed the device sequence.
 
@@ -15,6 +15,8 @@ import torch
 from conftest import GOLDEN
 
 sys.path.insert(0, GOLDEN)
+from segment_inputs import segment_inputs as _segment_inputs           # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 777.0
@@ -116,7 +118,7 @@ def _calib_ref64(x, ratio, ax=2.0, ay=2.0):
 def test_calib_baseline_matches_host(dev, T, ratio, negative):
     """Against the float64 statement of the operation (bar) and the host function itself (fp32 inside: the same bar around
     it).  Column 3 is constant, column 7 and the mouth column 148 hold every value twice (ties across the k boundary)."""
-    from animateportrait_amd import landmark_post as lp, module1 as m1
+    from animateportrait_amd import landmark_host as lh, landmark_post as lp
     rs = np.random.RandomState(T)
     x = rs.randn(T, 204).astype(np.float32)
     x[:, 3] = 1.25
@@ -125,7 +127,7 @@ def test_calib_baseline_matches_host(dev, T, ratio, negative):
     if negative:
         x = -np.abs(x) - 0.5
     ref = _calib_ref64(x, ratio, 2.0, 1.5)
-    host = m1.calib_baseline(x.astype(np.float64), 2.0, 1.5, ratio)
+    host = lh.calib_baseline(x.astype(np.float64), 2.0, 1.5, ratio)
     xb, xv, yb, yv = _guarded(x, dev)
     from animateportrait_amd import _seqapi as Q, ops
     Q.check(Q.lib().apq_calib_baseline(ops._ptr(xv), ops._ptr(yv), T, int(T * ratio), 2.0, 1.5, ops._stream()), 'calib_baseline')
@@ -139,36 +141,22 @@ def test_calib_baseline_matches_host(dev, T, ratio, negative):
 
 
 # ---------------------------------------------------------------------------------------------------------- segment assembly
-def _segment_inputs(T, inverted):
-    """dis, base, fid such that the assembled inner-lip polygon (points 60 .. 67) is a counter-clockwise octagon of area ~0.05
-    in every frame, mirrored in y (area ~-0.05) in the frames of ``inverted``."""
-    rs = np.random.RandomState(T)
-    fid = (rs.randn(68, 3) * 0.2).astype(np.float32)
-    ang = 2 * np.pi * np.arange(8) / 8
-    fid[60:68, 0], fid[60:68, 1] = 0.2 * np.cos(ang), 0.1 * np.sin(ang)
-    dis = (rs.randn(T, 204) * 0.01).astype(np.float32)
-    base = (rs.randn(T, 68, 3) * 0.01).astype(np.float32)
-    for j in inverted:
-        base[j, 60:68, 1] -= 2 * fid[60:68, 1]
-    return dis, base.reshape(T, 204), fid.reshape(1, 204)
-
-
 @pytest.mark.parametrize('T', [10, 113, 512])
 @pytest.mark.parametrize('which', ['first', 'second', 'last', 'run', 'none'])
 def test_segment_assemble_matches_host(dev, T, which):
     """close_pose_branch_mouth x amp + base + fid, then solve_inverse_lip, in one launch against the host statements on the same
     fp32 inputs.  Observed on the MI355X: all fifteen cases are bit equal to the host (L-inf 0): the kernel keeps numpy's fp32
     operation order and is built without multiply-add contraction.  The assertion is the bar all the same."""
-    from animateportrait_amd import landmark_post as lp, module1 as m1
+    from animateportrait_amd import landmark_host as lh, landmark_post as lp
     inverted = {'first': [0], 'second': [1], 'last': [T - 1], 'run': [5, 6, 7], 'none': []}[which]
     dis, base, fid = _segment_inputs(T, inverted)
     ratio, amp = 0.99, 0.5
-    seg = m1.close_pose_branch_mouth(dis.copy(), ratio).astype(np.float32) * np.float32(amp) + base + fid
+    seg = lh.close_pose_branch_mouth(dis.copy(), ratio).astype(np.float32) * np.float32(amp) + base + fid
     assert seg.dtype == np.float32
-    areas = np.array([m1._signed_area(seg[j].reshape(68, 3)[60:68, 0:2]) for j in range(T)])
+    areas = np.array([lh._signed_area(seg[j].reshape(68, 3)[60:68, 0:2]) for j in range(T)])
     # the condition of the comparison: no frame's branch can flip on rounding, and the inverted frames are the intended ones
     assert np.abs(areas).min() >= 1e-4 and sorted(np.nonzero(areas < 0)[0].tolist()) == inverted
-    ref = m1.solve_inverse_lip(seg.copy())
+    ref = lh.solve_inverse_lip(seg.copy())
     assert (len(inverted) > 0) == (not np.array_equal(ref, seg))
     d, b, f = (torch.from_numpy(a).to(dev) for a in (dis, base, fid))
     got = lp.segment_assemble(d, b, f, ratio, amp, close=True, lip=True, nose=False).cpu().numpy()
@@ -183,14 +171,14 @@ def test_segment_assemble_matches_host(dev, T, which):
 
 
 def test_segment_steps_alone_match_host(dev):
-    from animateportrait_amd import landmark_post as lp, module1 as m1
+    from animateportrait_amd import landmark_host as lh, landmark_post as lp
     dis, base, fid = _segment_inputs(113, [4, 5, 40])
     seg = (dis + base + fid).astype(np.float32)
     t = torch.from_numpy(seg).to(dev)
     keep = t.clone()
-    ref = m1.close_pose_branch_mouth(seg.copy(), 0.9)
+    ref = lh.close_pose_branch_mouth(seg.copy(), 0.9)
     assert _report('close_pose_branch_mouth', lp.close_pose_branch_mouth(t, 0.9).cpu().numpy(), ref) <= _bar(ref)
-    ref = m1.solve_inverse_lip(seg.copy())
+    ref = lh.solve_inverse_lip(seg.copy())
     assert not np.array_equal(ref, seg)
     assert _report('solve_inverse_lip', lp.solve_inverse_lip(t).cpu().numpy(), ref) <= _bar(ref)
     assert torch.equal(t, keep)                                  # out of place
@@ -200,10 +188,10 @@ def test_segment_steps_alone_match_host(dev):
 @pytest.mark.parametrize('T', [46, 200])
 def test_add_naive_eye_matches_host(dev, T):
     """T = 46: the single blink at frame 30, whose ramp reaches the last frame; T = 200: two blinks with RandomState(0)."""
-    from animateportrait_amd import landmark_post as lp, module1 as m1
+    from animateportrait_amd import landmark_host as lh, landmark_post as lp
     x = (np.random.RandomState(T).randn(T, 68, 3) * 30 + 128).astype(np.float32)
-    ref = m1.add_naive_eye(x.astype(np.float64), np.random.RandomState(0))
-    assert len(m1.blink_stamps(T, np.random.RandomState(0))) == (1 if T == 46 else 2)
+    ref = lh.add_naive_eye(x.astype(np.float64), np.random.RandomState(0))
+    assert len(lh.blink_stamps(T, np.random.RandomState(0))) == (1 if T == 46 else 2)
     t = torch.from_numpy(x).to(dev)
     got = lp.add_naive_eye(t, np.random.RandomState(0))
     assert got.is_cuda and got.shape == (T, 68, 3) and np.array_equal(t.cpu().numpy(), x)
@@ -296,6 +284,33 @@ def test_predict_landmarks_content_branch_on_device(dev, golden):
         m1.set_post_backend(prev)
     assert isinstance(host, np.ndarray) and torch.is_tensor(got) and got.is_cuda and got.shape == host.shape == (40, 68, 2)
     assert _report('predict_landmarks', got.cpu().numpy(), host) <= _bar(host)
+
+
+@pytest.mark.parametrize('T,segment,kept', [(40, 16, 32), (44, 16, 44)])
+def test_one_segment_loop_on_device_keeps_the_hosts_rows(dev, golden, T, segment, kept):
+    """The clip driver's one loop with the 'device' backend on short segments: 16, 16 and a dropped 8; 16, 16 and a kept 12.
+    Compared with the host backend as test_stage_on_device_matches_reference_golden does (no eyes: fewer than 46 rows)."""
+    from animateportrait_amd import module1 as m1
+    from test_module1_gpu import _nets
+    gd = golden('module1.npz')
+    netc, netg = _nets(gd, dev)
+    g = torch.Generator().manual_seed(T)
+    au, spk, fid = torch.randn(T, 18, 80, generator=g), torch.randn(256, generator=g), gd['fid'].view(-1)
+
+    def run():
+        fl = m1.predict_landmarks_speaker_aware(netg, netc, au, spk, fid, segment=segment)
+        return fl, m1.to_image_landmarks(fl, scale=0.01, shift=(-128.0, -120.0), eyes=False, rng=np.random.RandomState(0))
+    host_fl, host_img = run()
+    prev = m1.set_post_backend('device')
+    try:
+        fl, img = run()
+    finally:
+        m1.set_post_backend(prev)
+    assert isinstance(host_fl, np.ndarray) and host_fl.shape == (kept, 204)
+    assert torch.is_tensor(fl) and fl.is_cuda and fl.dtype == torch.float32 and fl.shape == (kept, 204)
+    assert torch.is_tensor(img) and img.is_cuda and img.shape == (kept, 68, 3)
+    _report('one loop T %d segment %d, device vs host landmarks' % (T, segment), fl.cpu().numpy(), host_fl)
+    assert _report('one loop T %d segment %d, image landmarks' % (T, segment), img.cpu().numpy(), host_img) <= _bar(host_img)
 
 
 # ------------------------------------------------------------------------------------------------------------- end to end

@@ -1,5 +1,5 @@
 """CPU (-m "not gpu"): the rigid landmark registration -- its float64 statement (tests/register_reference.py) against the golden
-the reference's own icp made (tests/golden/register.npz), the numpy twins of module1 against the statement, every refusal of
+the reference's own icp made (tests/golden/register.npz), the numpy twins of landmark_host (through module1) against the statement, every refusal of
 apq_rigid_register_ok by name, ``module1_train --use_reg_as_std --std_face`` on a tiny dump, and the clip driver with both
 head-stabilisation switches off."""
 import argparse
@@ -67,16 +67,16 @@ def test_jacobi_svd_orders_and_signs_like_lapack():
 
 
 def test_numpy_twins_equal_the_statement(gold):
-    from animateportrait_amd import module1 as m1
+    from animateportrait_amd import landmark_host as lh, module1 as m1
     fl, std = gold['frames'], gold['std']
-    assert m1.T_SHAPE_IDX == rr.T_SHAPE_IDX
+    assert lh.T_SHAPE_IDX == rr.T_SHAPE_IDX
     for centre, rot, flags in ((True, False, 1), (False, True, 2), (True, True, 3)):
         got = m1.stabilise_head(fl, std, centerize_face=centre, no_y_rotation=rot)
         assert got.dtype == np.float32 and got.shape == fl.shape and np.array_equal(got, rr.rigid_register(fl, std, flags)[0])
     assert m1.stabilise_head(fl, std) is fl                      # both off: nothing runs
     ref_out, ref_pose = rr.rigid_register(fl, std, 4)
     for i in range(fl.shape[0]):
-        assert np.abs(m1.icp_t_shape(fl[i], std) - ref_pose[i].reshape(3, 4)).max() <= 1e-12
+        assert np.abs(lh.icp_t_shape(fl[i], std) - ref_pose[i].reshape(3, 4)).max() <= 1e-12
         got = m1.register_face(fl[i], std)
         assert got.dtype == np.float32 and np.array_equal(got, ref_out[i])
     # a torch tensor on the CPU is served like an array
@@ -212,7 +212,7 @@ def test_flag_alone_is_still_refused(tmp_path):
 
 # -------------------------------------------------------------------------------------------------------- the clip driver
 def test_clip_driver_with_the_switches_off_is_unchanged(golden, monkeypatch):
-    from animateportrait_amd import module1 as m1
+    from animateportrait_amd import landmark_host as lh, module1 as m1
     from test_stream_cpu import _seeded
     gd = golden('module1.npz')
     netc = _seeded(m1.Audio2LandmarkContent(use_prior_net=True, drop_out=0.5), gd, 'c_', 78)
@@ -221,7 +221,7 @@ def test_clip_driver_with_the_switches_off_is_unchanged(golden, monkeypatch):
     au, spk, fid = torch.randn(40, 18, 80, generator=gp), torch.randn(256, generator=gp), gd['fid'].view(-1)
     on = m1.predict_landmarks_speaker_aware(netg, netc, au, spk, fid, centerize_face=True, no_y_rotation=True)
     # with both switches off nothing of the registration runs: the twins may not even be reached past their first line
-    monkeypatch.setattr(m1, 'icp_t_shape', lambda *a, **k: pytest.fail('icp ran with the switches off'))
+    monkeypatch.setattr(lh, 'icp_t_shape', lambda *a, **k: pytest.fail('icp ran with the switches off'))
     plain = m1.predict_landmarks_speaker_aware(netg, netc, au, spk, fid)
     off = m1.predict_landmarks_speaker_aware(netg, netc, au, spk, fid, centerize_face=False, no_y_rotation=False)
     assert plain.dtype == off.dtype == np.float32 and plain.shape == (40, 204) and np.array_equal(plain, off)

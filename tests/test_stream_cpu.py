@@ -54,7 +54,7 @@ def test_module1_clip_pipeline_matches_reference_methods(golden):
     """predict_landmarks_speaker_aware == the reference's __train_face_and_pos__ / __calib_baseline_pred_fls__ /
     __solve_inverse_lip2__ + the loop of __train_pass__ on a 600-window clip (two segments); the inverted-lip fix and
     add_naive_eye on their own against the reference functions."""
-    from animateportrait_amd import module1 as m1
+    from animateportrait_amd import landmark_host as lh, module1 as m1
     gd = golden('module1.npz')
     netc = _seeded(m1.Audio2LandmarkContent(use_prior_net=True, drop_out=0.5), gd, 'c_', 78)
     netg = _seeded(m1.Audio2LandmarkPos(drop_out=0.5), gd, 'g_', 79)
@@ -67,10 +67,10 @@ def test_module1_clip_pipeline_matches_reference_methods(golden):
     assert np.abs(fl[::16] - ref).max() < 2e-5 * np.abs(ref).max()
     assert abs(fl.sum() - float(gd['p_sum'])) < 1e-4 * float(gd['p_abs'])
     lips = gd['lip_in'].numpy().astype(np.float64)
-    fixed = m1.solve_inverse_lip(lips.copy())
+    fixed = lh.solve_inverse_lip(lips.copy())
     assert np.abs(fixed - gd['lip_out'].numpy()).max() < 1e-12 and np.abs(fixed - lips).max() > 0.1   # (some frames were fixed)
     np.random.seed(5)
-    eyes = m1.add_naive_eye(gd['eye_in'].numpy().copy())
+    eyes = lh.add_naive_eye(gd['eye_in'].numpy().copy())
     assert np.abs(eyes - gd['eye_out'].numpy()).max() < 1e-6
     img = m1.to_image_landmarks(fl, scale=0.01, shift=(-128.0, -120.0), rng=np.random.RandomState(1))
     assert img.shape == (600, 68, 3) and np.isfinite(img).all()

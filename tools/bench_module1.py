@@ -4,7 +4,7 @@ For the example clip's 625 windows (tests/golden/female12.wav; both landmark net
 seeded random weights, as bench.py's stream leg builds them) ``module1.predict_landmarks_speaker_aware`` is timed with both
 LSTM backends in ONE process, in alternated rounds, and split into
   (a) networks: the forward passes of the two networks, a device synchronise before and after each, and
-  (b) host:     everything else in the call -- the .cpu() copies, _savgol, calib_baseline, solve_inverse_lip.
+  (b) host:     everything else in the call -- the .cpu() copies and landmark_host (_savgol, calib_baseline, solve_inverse_lip).
 Medians over the rounds are reported.  Then the kernel alone: one apq_lstm_layer_fwd launch at B = 512, T = 18 and
 I in {80, 161, 256} between device events, next to a one-layer nn.LSTM of the same shape.
 
