@@ -82,6 +82,8 @@ SIGNATURES = {
                                               ctypes.POINTER(ApSrc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                               c_f32p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     'ap_conv2d_kernel_name': (ctypes.c_int, [ctypes.POINTER(ApConvDesc), ctypes.c_char_p, ctypes.c_int32]),
+    'ap_conv2d_fwd_route': (ctypes.c_int, [ctypes.POINTER(ApConvDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
+    'ap_conv2d_fwd_route_names': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32]),
     'ap_conv2d_pack_weights': (ctypes.c_int, [ctypes.POINTER(ApConvDesc), c_f32p, c_f32p, ctypes.c_void_p]),
     'ap_conv2d_pack_entry_bytes': (ctypes.c_int32, []),
     'ap_conv2d_pack_entries': (ctypes.c_int32, [ctypes.POINTER(ApConvDesc), ctypes.POINTER(ApWeightView), c_f32p, ctypes.c_void_p,

@@ -10,6 +10,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 namespace apamd {
 
@@ -17,6 +18,7 @@ namespace apamd {
 const void* bf3_sb_kernel(size_t* lds_bytes);     // tools/variants/conv_bf3_sb.hip
 #endif
 
+static const int kDirectCops[] = {1, 4};     // the instantiations of conv_direct_f32<DirectCfg<7, cop>>
 static const void* direct_fn(int K, int cop) {
     if (K == 7 && cop == 1) return reinterpret_cast<const void*>(&conv_direct_f32<DirectCfg<7, 1>>);
     if (K == 7 && cop == 4) return reinterpret_cast<const void*>(&conv_direct_f32<DirectCfg<7, 4>>);
@@ -41,11 +43,12 @@ struct FwdArgs {
     hipStream_t stream;
 };
 
-// Every refusal that depends on the arguments, before anything is launched; callers tell the refusals apart, so the order stays
-static int check_fwd_args(const ap_conv_desc* d, const Plan& pl, const OutForm& o, const FwdArgs& a) {
+// Every refusal that depends on the arguments, before anything is launched; callers tell the refusals apart, so the order stays.
+// a == null (ap_conv2d_fwd_route): the data pointers are taken as given, everything else is checked as for a launch
+static int check_fwd_args(const ap_conv_desc* d, const Plan& pl, const OutForm& o, const FwdArgs* a) {
     if (o.bf16 && (!ob16_plan_ok(d, pl) || o.octet))
         return fail(AP_ERR_UNSUPPORTED, "conv2d_fwd_bf16out: only the plain-bf16 dense 3x3 stride-1 layers store bf16 (ap_conv2d_bf16out_ok)");
-    if (!a.packed || !a.y) return fail(AP_ERR_INVALID, "null packed/y pointer");
+    if (a && (!a->packed || !a->y)) return fail(AP_ERR_INVALID, "null packed/y pointer");
     if (o.octet && !octet_plan_ok(d, pl))
         return fail(AP_ERR_UNSUPPORTED, "conv2d_fwd_octet: only single-launch split-bf16 layers of the run-time-tap / row kernel "
                                         "families with Cout %% 8 == 0 write the channel-octet layout (ap_conv2d_octet_ok)");
@@ -57,11 +60,24 @@ static int check_fwd_args(const ap_conv_desc* d, const Plan& pl, const OutForm& 
     }
     if (d->presplit && !pl.bf3) return fail(AP_ERR_INVALID, "desc.presplit set for a layer that does not take split sources");
     for (int s = 0; s < d->nsrc; ++s) {
-        if (!d->src[s].data) return fail(AP_ERR_INVALID, "segment %d: null data", s);
+        if (a && !d->src[s].data) return fail(AP_ERR_INVALID, "segment %d: null data", s);
         if ((d->src[s].mean == nullptr) != (d->src[s].rstd == nullptr))
             return fail(AP_ERR_INVALID, "segment %d: mean and rstd must be given together", s);
         if (d->src[s].act < 0 || d->src[s].act > 2) return fail(AP_ERR_INVALID, "segment %d: act %d", s, d->src[s].act);
     }
+    return AP_OK;
+}
+
+// conv_tsmall_f32<CO> is instantiated for these output widths; a layer runs on the narrowest one that holds its channels
+static const int kTSmallCouts[] = {1, 2, 4};
+static int tsmall_inst(int Cout) {
+    for (int c : kTSmallCouts)
+        if (Cout <= c) return c;
+    return 0;
+}
+
+static int tsmall_grid_ok(const ap_conv_desc* d) {
+    if (d->N > 65535 || (d->H + 7) / 8 > 65535) return fail(AP_ERR_UNSUPPORTED, "conv_tsmall: grid too large");
     return AP_OK;
 }
 
@@ -71,11 +87,13 @@ static int launch_tsmall(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a
     fill_seg(p.src, d->src[0], 0);
     p.N = d->N; p.C = pl.Cin; p.H = d->H; p.W = d->W; p.Cout = d->Cout;
     p.w = a.packed + pl.head_w_off; p.bias = a.bias; p.act = d->act; p.y = a.y;
-    if (d->N > 65535 || (d->H + 7) / 8 > 65535) return fail(AP_ERR_UNSUPPORTED, "conv_tsmall: grid too large");
+    if (int rc = tsmall_grid_ok(d)) return rc;
     const dim3 grid((d->W + 31) / 32, (d->H + 7) / 8, d->N);
-    if (d->Cout == 1) hipLaunchKernelGGL((conv_tsmall_f32<1>), grid, dim3(256), 0, a.stream, p);
-    else if (d->Cout == 2) hipLaunchKernelGGL((conv_tsmall_f32<2>), grid, dim3(256), 0, a.stream, p);
-    else hipLaunchKernelGGL((conv_tsmall_f32<4>), grid, dim3(256), 0, a.stream, p);
+    switch (tsmall_inst(d->Cout)) {
+        case 1: hipLaunchKernelGGL((conv_tsmall_f32<1>), grid, dim3(256), 0, a.stream, p); break;
+        case 2: hipLaunchKernelGGL((conv_tsmall_f32<2>), grid, dim3(256), 0, a.stream, p); break;
+        default: hipLaunchKernelGGL((conv_tsmall_f32<4>), grid, dim3(256), 0, a.stream, p); break;
+    }
     return check_launch("conv_tsmall_f32");
 }
 
@@ -83,15 +101,21 @@ static int launch_tsmall(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a
 // 16 FMAs per staged row element, on RB + 3 rows for RB outputs) and a launch is a few hundred 1024-thread workgroups: what counts
 // is the number of workgroup ROUNDS on the CUs times the rows a workgroup stages.  (Round 6; before: 3-row bands unless taller
 // ones still gave >= 200 workgroups -- 320 workgroups = two rounds at 2B = 32, 160 = 5/8 of the chip at B = 16.)
-static int launch_head(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+static const int kHeadRows[] = {2, 3, 4, 5, 6, 10};      // the instantiations of conv_head_fwd_kernel<RB>
+static int head_rows(int N, int Hout) {
     const int cus = num_cus();
     int rb = 3;
     long long best_cost = -1;
-    for (int cand : {2, 3, 4, 5, 6, 10}) {
-        const long long wgs = (long long)d->N * ((pl.Hout + cand - 1) / cand);
+    for (int cand : kHeadRows) {
+        const long long wgs = (long long)N * ((Hout + cand - 1) / cand);
         const long long cost = ((wgs + cus - 1) / cus) * (cand + 3);
         if (best_cost < 0 || cost < best_cost) { rb = cand; best_cost = cost; }
     }
+    return rb;
+}
+
+static int launch_head(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+    const int rb = head_rows(d->N, pl.Hout);
     HeadParams p;
     memset(&p, 0, sizeof(p));
     fill_seg(p.src, d->src[0], 0);
@@ -109,6 +133,11 @@ static int launch_head(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) 
     return check_launch("conv_head_fwd_kernel");
 }
 
+// the instantiations of the narrow 3x3 kernels: {stride, Cout}; stride 1 stages its tile in LDS (conv_small_f32), stride 2 gathers
+// (conv_small_gather_f32)
+static const int kSmallCfgs[][2] = {{1, 8}, {1, 16}, {2, 8}, {2, 16}};
+static bool small_gathers(int stride) { return stride != 1; }
+
 static int launch_small(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
     SmallKParams p;
     memset(&p, 0, sizeof(p));
@@ -119,8 +148,8 @@ static int launch_small(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a)
     p.stats = a.stats; p.stat_tiles = pl.stat_tiles;
     p.tiles_x = (pl.Wout + 31) / 32; p.tiles_y = (pl.Hout + 7) / 8;
     const dim3 grid((unsigned)((long long)d->N * p.tiles_y * p.tiles_x));
-    if (d->stride == 1 && d->Cout == 8) hipLaunchKernelGGL((conv_small_f32<SmallCfg<1, 8>>), grid, dim3(256), 0, a.stream, p);
-    else if (d->stride == 1) hipLaunchKernelGGL((conv_small_f32<SmallCfg<1, 16>>), grid, dim3(256), 0, a.stream, p);
+    if (!small_gathers(d->stride) && d->Cout == 8) hipLaunchKernelGGL((conv_small_f32<SmallCfg<1, 8>>), grid, dim3(256), 0, a.stream, p);
+    else if (!small_gathers(d->stride)) hipLaunchKernelGGL((conv_small_f32<SmallCfg<1, 16>>), grid, dim3(256), 0, a.stream, p);
     else if (d->Cout == 8) hipLaunchKernelGGL((conv_small_gather_f32<SmallCfg<2, 8>>), grid, dim3(256), 0, a.stream, p);
     else hipLaunchKernelGGL((conv_small_gather_f32<SmallCfg<2, 16>>), grid, dim3(256), 0, a.stream, p);
     return check_launch("conv_small_f32");
@@ -128,12 +157,26 @@ static int launch_small(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a)
 
 // The generator's output layer in split-bf16 arithmetic -- one reflection-padded 64-channel source, one output channel, no
 // statistics epilogue -- multiplies on the matrix pipe (conv_tapgemm.h).  Same plan, same packed image: chosen here, at launch.
-static bool tapgemm_serves(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
+static bool tapgemm_serves(const ap_conv_desc* d, const Plan& pl, bool with_stats) {
     return d->precision == AP_PRECISION_BF16X3 && d->Cout == 1 && d->KH == 7 && d->nsrc == 1 && d->src[0].C == TapGemmCfg::C &&
-           d->pad_mode == AP_PAD_REFLECT && !a.stats && pl.cin_pad == TapGemmCfg::C;
+           d->pad_mode == AP_PAD_REFLECT && !with_stats && pl.cin_pad == TapGemmCfg::C;
 }
 
 // Tile height: the workgroups (two per CU) run in rounds, and a workgroup stages th + 6 rows for th output rows
+static int tapgemm_tiles_x(const Plan& pl) { return (pl.Wout + TapGemmCfg::TW - 1) / TapGemmCfg::TW; }
+static int tapgemm_band(int N, int Hout, int tiles_x) {
+    const long long slots = 2LL * num_cus();
+    long long best_cost = -1;
+    int best = Hout;
+    for (int ty = 1; ty <= (Hout + 7) / 8; ++ty) {
+        const int th = (Hout + ty - 1) / ty;
+        const long long wgs = (long long)N * tiles_x * ((Hout + th - 1) / th);
+        const long long cost = ((wgs + slots - 1) / slots) * (th + 6);
+        if (best_cost < 0 || cost < best_cost) { best = th; best_cost = cost; }
+    }
+    return best;
+}
+
 static int launch_tapgemm(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
     const void* kfn = tapgemm_kernel();
     int rc = ensure_dyn_lds(kfn, 160 * 1024);
@@ -143,15 +186,8 @@ static int launch_tapgemm(const ap_conv_desc* d, const Plan& pl, const FwdArgs& 
     fill_seg(p.seg, d->src[0], 0);
     p.N = d->N; p.H = d->H; p.W = d->W;
     p.y = a.y; p.wp = a.packed; p.bias = a.bias; p.act = d->act;
-    p.tiles_x = (pl.Wout + TapGemmCfg::TW - 1) / TapGemmCfg::TW;
-    const long long slots = 2LL * num_cus();
-    long long best_cost = -1;
-    for (int ty = 1; ty <= (pl.Hout + 7) / 8; ++ty) {
-        const int th = (pl.Hout + ty - 1) / ty;
-        const long long wgs = (long long)d->N * p.tiles_x * ((pl.Hout + th - 1) / th);
-        const long long cost = ((wgs + slots - 1) / slots) * (th + 6);
-        if (best_cost < 0 || cost < best_cost) { p.th = th; best_cost = cost; }
-    }
+    p.tiles_x = tapgemm_tiles_x(pl);
+    p.th = tapgemm_band(d->N, pl.Hout, p.tiles_x);
     p.tiles_y = (pl.Hout + p.th - 1) / p.th;
     void* args[] = {&p};
     hipError_t e = hipLaunchKernel(kfn, dim3((unsigned)(d->N * p.tiles_y * p.tiles_x)), dim3(256), args, TapGemmCfg::lds_bytes(), a.stream);
@@ -160,7 +196,6 @@ static int launch_tapgemm(const ap_conv_desc* d, const Plan& pl, const FwdArgs& 
 }
 
 static int launch_direct(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
-    if (tapgemm_serves(d, pl, a)) return launch_tapgemm(d, pl, a);
     const void* kfn = direct_fn(d->KH, pl.direct_cop);
     int rc = ensure_dyn_lds(kfn, 160 * 1024);
     if (rc) return rc;
@@ -212,16 +247,24 @@ static int tap_bits(const Launch& L, unsigned& bits) {
     return AP_OK;
 }
 
+// what launch L of an implicit-GEMM plan cannot be; bits: ConvKParams.tap_bits of a run-time-tap kernel
+static int igemm_launch_ok(const ap_conv_desc* d, const Plan& pl, const Launch& L, unsigned& bits) {
+    int rc;
+    bits = 0;
+    if (pl.k->K == 0 && (rc = tap_bits(L, bits))) return rc;
+    if ((long long)d->N * L.tiles_y * L.tiles_x * pl.co_tiles > 0x7fffffffLL) return fail(AP_ERR_UNSUPPORTED, "grid too large");
+    return AP_OK;
+}
+
 static int launch_igemm(const ap_conv_desc* d, const Plan& pl, const FwdArgs& a) {
     int rc = ensure_dyn_lds(pl.k->fn, 160 * 1024);
     if (rc) return rc;
     for (const auto& L : pl.launches) {
         ConvKParams p = conv_params(d, pl, L, a, true);
         p.wfloats = pl.k->wfloats(p.ntaps);
-        if (pl.k->K == 0 && (rc = tap_bits(L, p.tap_bits))) return rc;
+        if ((rc = igemm_launch_ok(d, pl, L, p.tap_bits))) return rc;
         const size_t lds = 4 * pl.k->lds_floats(p.ntaps, p.nchunks > 1 ? 2 : 1, p.cin_pad);
         const long long nblk = (long long)d->N * L.tiles_y * L.tiles_x * pl.co_tiles;
-        if (nblk > 0x7fffffffLL) return fail(AP_ERR_UNSUPPORTED, "grid too large");
         void* args[] = {&p};
         hipError_t e = hipLaunchKernel(pl.k->fn, dim3((unsigned)nblk), dim3(256), args, lds, a.stream);
         if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "conv_igemm_f32 launch: %s", hipGetErrorString(e));
@@ -263,10 +306,11 @@ static int check_ph4_plan(const Plan& pl, const ap_out_view* view) {
 
 // one launch (phase 0's geometry) covers the four phases: their weight blocks follow each other in the packed image, so the
 // virtual cout tile indexes them directly (conv_ph4 walks the real cout tiles)
+static int launch_co_tiles(const Plan& pl) { return pl.fused_phases && !pl.ph4 ? 4 * pl.co_tiles : pl.co_tiles; }
 static void fused_phase_params(ConvKParams& p, const Plan& pl) {
     p.nphase = 4;
     p.co_tiles_phase = pl.co_tiles;
-    p.co_tiles = pl.ph4 ? pl.co_tiles : 4 * pl.co_tiles;
+    p.co_tiles = launch_co_tiles(pl);
     for (int ph = 0; ph < 4; ++ph) {
         const Launch& Lp = pl.launches[ph];
         p.ph_dy0[ph] = Lp.dy0; p.ph_dx0[ph] = Lp.dx0; p.ph_oy[ph] = Lp.oy_off; p.ph_ox[ph] = Lp.ox_off;
@@ -276,9 +320,13 @@ static void fused_phase_params(ConvKParams& p, const Plan& pl) {
 }
 
 // space-to-depth form of a 3x3 stride-2 layer: input phase (ry, rx) = 16-channel chunks [r C/16, (r+1) C/16)
-static void s2d3_params(ConvKParams& p, const ap_conv_desc* d, const Plan& pl) {
-    if (d->s2d_k != 3 || d->transposed || pl.bk->K != 0 || d->KW != 2 || d->nsrc != 1 || d->src[0].C % 64 != 0) return;
-    p.s2d_div = d->src[0].C / 64;
+static int s2d3_div(const ap_conv_desc* d, const Plan& pl) {
+    if (d->s2d_k != 3 || d->transposed || pl.bk->K != 0 || d->KW != 2 || d->nsrc != 1 || d->src[0].C % 64 != 0) return 0;
+    return d->src[0].C / 64;
+}
+static void s2d3_params(ConvKParams& p, int div) {
+    if (div <= 0) return;
+    p.s2d_div = div;
     for (int r = 0; r < 4; ++r) {
         p.s2d_mask[r] = 0;
         for (int t = 0; t < 4; ++t)
@@ -298,40 +346,87 @@ static unsigned bf3_workgroups(long long tiles, size_t lds, bool two_per_cu) {
     return (unsigned)(tiles > cus ? cus : tiles);
 }
 
-static int launch_bf3(const ap_conv_desc* d, const Plan& pl, const OutForm& o, const FwdArgs& a) {
+// What one split-bf16 launch runs: decided here for the launcher and for ap_conv2d_fwd_route alike
+struct Bf3Launch {
+    const Bf3Kernel* kern;
+    const void* kfn;
+    bool s2d3_ct;          // kfn is the instantiation with the compile-time tap sets of a space-to-depth 3x3 layer
+    int s2d_div;           // > 0: space-to-depth 3x3 layer, C / 64 chunks per input phase
+    unsigned tap_bits;
+    int tiles_x, tiles_y, co_tiles;
+    size_t lds;
+};
+
+static int bf3_choose(const ap_conv_desc* d, const Plan& pl, const OutForm& o, const Launch& L, Bf3Launch& c) {
+    const int ntaps = (int)L.taps.size();
+    c.kern = pl.ph4 ? pl.bk : bf3_for_taps(pl.bk, ntaps);
+    if (!c.kern) return fail(AP_ERR_UNSUPPORTED, "no split-bf16 kernel for a phase with %d taps", ntaps);
+    c.tiles_x = L.tiles_x; c.tiles_y = L.tiles_y;
+    if (const ap_out_view* v = o.view) {
+        c.tiles_x = (v->OW + 31) / 32;
+        c.tiles_y = (v->OH + pl.bk->TH - 1) / pl.bk->TH;
+    }
+    c.co_tiles = launch_co_tiles(pl);
+    c.s2d_div = s2d3_div(d, pl);
+    c.tap_bits = 0;
+    int rc;
+    if (pl.bk->K == 0 && (rc = tap_bits(L, c.tap_bits))) return rc;
+    c.kfn = o.bf16 ? c.kern->fn1_ob16 : c.kern->kernel(d->precision);
+    // even chunk count per input phase: the instantiation with compile-time tap sets (no fragment reads for absent taps)
+    c.s2d3_ct = c.s2d_div > 0 && (c.s2d_div & 1) == 0 && pl.nchunks == 4 * c.s2d_div && c.kern->kernel_s2d3(d->precision);
+    if (c.s2d3_ct) c.kfn = c.kern->kernel_s2d3(d->precision);
+    c.lds = c.kern->lds(d->precision, ntaps);
+    return AP_OK;
+}
+
+// what the split-bf16 pipeline cannot take, whatever the kernel (lds: with whatever a hook added)
+static int bf3_fits(const ap_conv_desc* d, const Plan& pl, size_t lds) {
+    if (lds > 160 * 1024) return fail(AP_ERR_UNSUPPORTED, "bf16x3 LDS tile of %zu bytes does not fit", lds);
+    if (pl.nchunks < 2) return fail(AP_ERR_UNSUPPORTED, "bf16x3 pipeline needs >= 32 input channels");
+    if (((long long)d->H * d->W + 1) * 32 >= (1LL << 31))   // per-lane DMA offsets span two channel-group planes
+        return fail(AP_ERR_UNSUPPORTED, "split-bf16 path: %d x %d planes are too large", d->H, d->W);
+    return AP_OK;
+}
+
+// the launches of a split-bf16 plan, in order: each(L, c) launches or describes one; a fused plan has one for its four phases
+template <class Each>
+static int bf3_launches(const ap_conv_desc* d, const Plan& pl, const OutForm& o, Each&& each) {
     if (!d->presplit)
         return fail(AP_ERR_INVALID, "this layer runs on the split-bf16 path: pass sources prepared by "
                                     "ap_split_prepass and set desc.presplit (see ap_conv2d_wants_presplit)");
     int rc = pl.ph4 ? check_ph4_plan(pl, o.view) : AP_OK;
     if (rc) return rc;
     for (const auto& L : pl.launches) {
-        const Bf3Kernel* kern = pl.ph4 ? pl.bk : bf3_for_taps(pl.bk, (int)L.taps.size());
-        if (!kern) return fail(AP_ERR_UNSUPPORTED, "no split-bf16 kernel for a phase with %d taps", (int)L.taps.size());
+        Bf3Launch c;
+        if ((rc = bf3_choose(d, pl, o, L, c)) || (rc = each(L, c))) return rc;
+        if (pl.fused_phases) break;
+    }
+    return AP_OK;
+}
+
+static int launch_bf3(const ap_conv_desc* d, const Plan& pl, const OutForm& o, const FwdArgs& a) {
+    return bf3_launches(d, pl, o, [&](const Launch& L, const Bf3Launch& c) -> int {
         ConvKParams p = conv_params(d, pl, L, a, false);
         p.wfloats = pl.bk->wfloats(p.ntaps);
         p.o_octet = o.octet ? 1 : 0;
         if (const ap_out_view* v = o.view) {
             // output window: a sub-grid of the output, stored with the caller's strides (ap_out_view)
             p.OH = v->OH; p.OW = v->OW;
-            p.tiles_x = (v->OW + 31) / 32;
-            p.tiles_y = (v->OH + pl.bk->TH - 1) / pl.bk->TH;
             p.o_nstride = v->nstride; p.o_cstride = v->cstride; p.o_rstride = v->rstride;
             p.osy = 1; p.oy_off = v->y_off;
             p.osx = v->xstride; p.ox_off = v->x_off * v->xstride;
         }
+        p.tiles_x = c.tiles_x; p.tiles_y = c.tiles_y;
         if (pl.fused_phases) fused_phase_params(p, pl);
-        s2d3_params(p, d, pl);
-        if (pl.bk->K == 0 && (rc = tap_bits(L, p.tap_bits))) return rc;
-        const void* kfn = o.bf16 ? kern->fn1_ob16 : kern->kernel(d->precision);
-        // even chunk count per input phase: the instantiation with compile-time tap sets (no fragment reads for absent taps)
-        if (p.s2d_div > 0 && (p.s2d_div & 1) == 0 && p.nchunks == 4 * p.s2d_div && kern->kernel_s2d3(d->precision))
-            kfn = kern->kernel_s2d3(d->precision);
-        rc = ensure_dyn_lds(kfn, 160 * 1024);
+        s2d3_params(p, c.s2d_div);
+        p.tap_bits = c.tap_bits;
+        const void* kfn = c.kfn;
+        int rc = ensure_dyn_lds(kfn, 160 * 1024);
         if (rc) return rc;
-        size_t lds = kern->lds(d->precision, p.ntaps);
+        size_t lds = c.lds;
         bool sb = false;
 #ifdef APAMD_VARIANTS
-        if (!o.view && !o.octet && kern->K == 3 && kern->S == 1 && kern->TH == 16 && !kern->ROW && d->precision != AP_PRECISION_BF16 &&
+        if (!o.view && !o.octet && c.kern->K == 3 && c.kern->S == 1 && c.kern->TH == 16 && !c.kern->ROW && d->precision != AP_PRECISION_BF16 &&
             p.osx == 1 && p.osy == 1 && p.oy_off == 0 && p.ox_off == 0 && env_int("APAMD_CONV_SB", 0)) {
             // rejected experiment kept for A/B (tools/variants/conv_bf16x3_sb.h, `make variants`): one LDS stage per
             // workgroup, two workgroups per CU
@@ -355,17 +450,25 @@ static int launch_bf3(const ap_conv_desc* d, const Plan& pl, const OutForm& o, c
             }
         }
 #endif
-        if (lds > 160 * 1024) return fail(AP_ERR_UNSUPPORTED, "bf16x3 LDS tile of %zu bytes does not fit", lds);
-        if (p.nchunks < 2) return fail(AP_ERR_UNSUPPORTED, "bf16x3 pipeline needs >= 32 input channels");
-        if (((long long)d->H * d->W + 1) * 32 >= (1LL << 31))   // per-lane DMA offsets span two channel-group planes
-            return fail(AP_ERR_UNSUPPORTED, "split-bf16 path: %d x %d planes are too large", d->H, d->W);
-        const unsigned nblk = bf3_workgroups((long long)d->N * p.tiles_y * p.tiles_x * p.co_tiles, lds, sb);
+        if ((rc = bf3_fits(d, pl, lds))) return rc;
+        const unsigned nblk = bf3_workgroups((long long)d->N * c.tiles_y * c.tiles_x * c.co_tiles, lds, sb);
         void* args[] = {&p};
         hipError_t e = hipLaunchKernel(kfn, dim3(nblk), dim3(256), args, lds, a.stream);
         if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "conv_bf16x3 launch: %s", hipGetErrorString(e));
-        if (pl.fused_phases) break;
-    }
-    return AP_OK;
+        return AP_OK;
+    });
+}
+
+// Which launcher serves a plan.  With a statistics epilogue wanted the two narrow-output layers stay on the general kernel, and
+// the last 7x7 layer on the vector ALUs
+enum class FwdFamily { TSmall, Head, Small, Bf3, TapGemm, Direct, Igemm };
+static FwdFamily fwd_family(const ap_conv_desc* d, const Plan& pl, bool with_stats) {
+    if (pl.tsmall && !with_stats) return FwdFamily::TSmall;
+    if (pl.head && !with_stats) return FwdFamily::Head;
+    if (pl.small) return FwdFamily::Small;
+    if (pl.bf3) return FwdFamily::Bf3;
+    if (pl.direct_cop) return tapgemm_serves(d, pl, with_stats) ? FwdFamily::TapGemm : FwdFamily::Direct;
+    return FwdFamily::Igemm;
 }
 
 // Every forward entry point: plan, refuse what the plan or the arguments rule out, then the family's launcher
@@ -373,15 +476,105 @@ static int conv2d_fwd_impl(const ap_conv_desc* d, const OutForm& o, const FwdArg
     Plan pl;
     int rc = make_plan(d, pl);
     if (rc) return rc;
-    rc = check_fwd_args(d, pl, o, a);
+    rc = check_fwd_args(d, pl, o, &a);
     if (rc) return rc;
-    // (with a statistics epilogue wanted the two narrow-output layers stay on the general kernel)
-    if (pl.tsmall && !a.stats) return launch_tsmall(d, pl, a);
-    if (pl.head && !a.stats) return launch_head(d, pl, a);
-    if (pl.small) return launch_small(d, pl, a);
-    if (pl.bf3) return launch_bf3(d, pl, o, a);
-    if (pl.direct_cop) return launch_direct(d, pl, a);
-    return launch_igemm(d, pl, a);
+    switch (fwd_family(d, pl, a.stats != nullptr)) {
+        case FwdFamily::TSmall: return launch_tsmall(d, pl, a);
+        case FwdFamily::Head: return launch_head(d, pl, a);
+        case FwdFamily::Small: return launch_small(d, pl, a);
+        case FwdFamily::Bf3: return launch_bf3(d, pl, o, a);
+        case FwdFamily::TapGemm: return launch_tapgemm(d, pl, a);
+        case FwdFamily::Direct: return launch_direct(d, pl, a);
+        default: return launch_igemm(d, pl, a);
+    }
+}
+
+// ------------------------------------------------------------------ the launch as text (ap_conv2d_fwd_route)
+// A kernel's word: the registries' names without their blanks
+static std::string word_of(const char* name) {
+    std::string w;
+    for (const char* c = name; *c; ++c)
+        if (*c != ' ') w += *c;
+    return w;
+}
+static std::string igemm_word(const ConvKernelInfo& k) {
+    char name[64];
+    snprintf(name, sizeof(name), "ConvCfg<%d,%d,%d,%d,%d,%d,%d>", k.CI, k.S, k.K, k.WCO, k.MT, k.WPX, k.NT);
+    return name;
+}
+static std::string num(long long v) { return std::to_string(v); }
+// name<a> / name<a,b>
+static std::string inst(const char* name, int a) { return std::string(name) + "<" + num(a) + ">"; }
+static std::string inst(const char* name, int a, int b) { return std::string(name) + "<" + num(a) + "," + num(b) + ">"; }
+
+// what conv2d_fwd_impl would launch for this descriptor and output form, from the launchers' own decisions: nothing is launched
+// and no pointer is followed
+static int fwd_route_text(const ap_conv_desc* d, int with_stats, int out_form, char* buf, int n) {
+    Plan pl;
+    int rc = make_plan(d, pl);
+    if (rc) return rc;
+    if (!buf || n < 1) return fail(AP_ERR_INVALID, "fwd_route: bad buffer");
+    if (out_form < 0 || out_form > 4) return fail(AP_ERR_INVALID, "fwd_route: out_form %d", out_form);
+    if (out_form >= 3 && with_stats) return fail(AP_ERR_INVALID, "fwd_route: the view forms take no statistics buffer");
+    // a window's size does not change the kernel: the whole output stands for every window
+    ap_out_view whole;
+    memset(&whole, 0, sizeof(whole));
+    whole.OH = pl.Hout; whole.OW = pl.Wout; whole.xstride = 1;
+    OutForm o;
+    o.view = out_form >= 3 ? &whole : nullptr;
+    o.octet = out_form == 1;
+    o.bf16 = out_form == 2 || out_form == 4;
+    if ((rc = check_fwd_args(d, pl, o, nullptr))) return rc;
+    std::string text;
+    switch (fwd_family(d, pl, with_stats != 0)) {
+        case FwdFamily::TSmall:
+            if ((rc = tsmall_grid_ok(d))) return rc;
+            text = inst("tsmall", tsmall_inst(d->Cout));
+            break;
+        case FwdFamily::Head: text = inst("head", head_rows(d->N, pl.Hout)); break;
+        case FwdFamily::Small: text = inst("small", d->stride, d->Cout) + (small_gathers(d->stride) ? " gather" : " staged"); break;
+        case FwdFamily::TapGemm: text = "tapgemm th=" + num(tapgemm_band(d->N, pl.Hout, tapgemm_tiles_x(pl))); break;
+        case FwdFamily::Direct: text = inst("direct", d->KH, pl.direct_cop); break;
+        case FwdFamily::Bf3:
+            rc = bf3_launches(d, pl, o, [&](const Launch& L, const Bf3Launch& c) -> int {
+                int r = bf3_fits(d, pl, c.lds);
+                if (r) return r;
+                if (!text.empty()) text += "; ";
+                text += "bf3 " + word_of(c.kern->name) + " taps=" + num((long long)L.taps.size()) +
+                        (d->precision == AP_PRECISION_BF16 ? " b16" : " x3") + (o.bf16 ? " ob16" : "");
+                if (c.s2d_div > 0) text += c.s2d3_ct ? " s2d3=ct" : " s2d3=mask";
+                if (pl.launches.size() > 1) text += pl.ph4 ? " phases=ph4" : (pl.fused_phases ? " phases=fused" : " phases=4launch");
+                text += " wg=" + num(bf3_workgroups((long long)d->N * c.tiles_y * c.tiles_x * c.co_tiles, c.lds, false));
+                return AP_OK;
+            });
+            if (rc) return rc;
+            break;
+        default:
+            for (const auto& L : pl.launches) {
+                unsigned bits;
+                if ((rc = igemm_launch_ok(d, pl, L, bits))) return rc;
+                if (!text.empty()) text += "; ";
+                text += "igemm " + igemm_word(*pl.k) + " taps=" + num((long long)L.taps.size());
+            }
+    }
+    snprintf(buf, n, "%s", text.c_str());
+    return AP_OK;
+}
+
+// every kernel word ap_conv2d_fwd_route can produce, one per line: the fixed instantiation lists of the small families and the registries
+static int fwd_route_names(char* buf, int n) {
+    if (!buf || n < 1) return fail(AP_ERR_INVALID, "fwd_route_names: bad buffer");
+    std::string all;
+    for (int c : kTSmallCouts) all += inst("tsmall", c) + "\n";
+    for (int rb : kHeadRows) all += inst("head", rb) + "\n";
+    for (const auto& c : kSmallCfgs) all += inst("small", c[0], c[1]) + "\n";
+    for (int cop : kDirectCops) all += inst("direct", 7, cop) + "\n";
+    all += "tapgemm\n";
+    for (const auto& k : registry()) all += igemm_word(k) + "\n";
+    for (const auto& k : bf3_registry()) all += word_of(k.name) + "\n";
+    for (int kk : {3, 4}) all += word_of(ph4_kernel(kk)->name) + "\n";
+    snprintf(buf, n, "%s", all.c_str());
+    return (int)all.size() < n ? AP_OK : fail(AP_ERR_INVALID, "fwd_route_names: %d bytes needed", (int)all.size() + 1);
 }
 
 }  // namespace apamd
@@ -416,6 +609,12 @@ int ap_conv2d_fwd_bf16out(const ap_conv_desc* d, const float* packed, const floa
     o.bf16 = true;
     return conv2d_fwd_impl(d, o, {packed, bias, reinterpret_cast<float*>(y_bf16), stat_partials, (hipStream_t)stream});
 }
+
+int ap_conv2d_fwd_route(const ap_conv_desc* d, int32_t with_stats, int32_t out_form, char* buf, int32_t buflen) {
+    return fwd_route_text(d, with_stats, out_form, buf, buflen);
+}
+
+int ap_conv2d_fwd_route_names(char* buf, int32_t buflen) { return fwd_route_names(buf, buflen); }
 
 int ap_conv2d_fwd_view_bf16out(const ap_conv_desc* d, const ap_out_view* view, const float* packed, const float* bias, void* y_bf16,
                                ap_stream_t stream) {

@@ -50,6 +50,9 @@ struct Plan {
 };
 
 int make_plan(const ap_conv_desc* d, Plan& pl);
+// the tables make_plan picks from (ap_conv2d_fwd_route_names lists them; ph4_kernel: conv_bf3_registry.h)
+const std::vector<ConvKernelInfo>& registry();
+const std::vector<Bf3Kernel>& bf3_registry();
 // the kernel of one launch: K == 0 kernels are instantiated per tap count
 const Bf3Kernel* bf3_for_taps(const Bf3Kernel* k, int ntaps);
 // which plans take the channel-octet / the bf16-output form (ap_conv2d_octet_ok, ap_conv2d_bf16out_ok; the launchers refuse the rest)

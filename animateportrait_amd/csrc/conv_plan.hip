@@ -8,7 +8,7 @@
 
 namespace apamd {
 
-static const std::vector<ConvKernelInfo>& registry() {
+const std::vector<ConvKernelInfo>& registry() {
     static std::vector<ConvKernelInfo> v;
     static std::once_flag once;
     std::call_once(once, [] {
@@ -29,7 +29,7 @@ static const ConvKernelInfo* find_kernel(int CI, int S, int K, int CO_TILE) {
 }
 
 // split-bf16 kernels (conv_bf16x3.h, conv_ph4.h): instantiated per tile family in conv_bf3_inst_*.hip / conv_ph4_inst.hip
-static const std::vector<Bf3Kernel>& bf3_registry() {
+const std::vector<Bf3Kernel>& bf3_registry() {
     static std::vector<Bf3Kernel> v;
     static std::once_flag once;
     std::call_once(once, [] {

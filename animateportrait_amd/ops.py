@@ -670,6 +670,21 @@ K7_WGRAD = os.environ.get('APAMD_NO_K7_WGRAD', '0') != '1'
 D0_MFMA = K7_WGRAD and os.environ.get('APAMD_NO_D0_MFMA', '0') != '1'
 
 
+OUT_PLAIN, OUT_OCTET, OUT_BF16, OUT_VIEW, OUT_VIEW_BF16 = range(5)      # out_form of ap_conv2d_fwd_route
+
+
+def conv_fwd_route(spec, n, h, w, with_stats=False, out_form=OUT_PLAIN):
+    """What the forward entry point of ``out_form`` would launch for this layer at this input size, as ap_conv2d_fwd_route words
+    it (a query: nothing is launched, no tensor is needed).  For the tests, which state the kernel a case is meant to exercise;
+    the product path does not ask."""
+    d = spec.desc(n, h, w)
+    if spec.precision != PRECISION_FP32 and C.check(C.lib().ap_conv2d_wants_presplit(ctypes.byref(d)), 'wants_presplit'):
+        d.presplit = 1
+    buf = ctypes.create_string_buffer(512)
+    C.check(C.lib().ap_conv2d_fwd_route(ctypes.byref(d), int(with_stats), out_form, buf, len(buf)), 'conv2d_fwd_route')
+    return buf.value.decode()
+
+
 def _conv2d_view(spec, srcs, packed, out, view):
     """ap_conv2d_fwd_view: the split-bf16 convolution ``spec`` of ``srcs`` into a window of ``out`` (no bias, no
     activation, no statistics)."""

@@ -239,6 +239,26 @@ int ap_norm_apply_split_ex(const ap_src* src, const float* stat_partials, int32_
  * rocprofv3 kernel trace), e.g. "ConvCfg<4, 1, 3, 2, 2, 2, 2>"; used by bench.py to attribute time per kernel */
 int ap_conv2d_kernel_name(const ap_conv_desc* d, char* buf, int32_t buflen);
 
+/* What the forward entry point of an output form would LAUNCH for `d`, as text; launches nothing and follows no pointer (source
+ * data pointers may be null; a segment's mean / rstd only say whether it is virtual).  with_stats: a statistics buffer is
+ * passed.  out_form: 0 ap_conv2d_fwd, 1 ..._octet, 2 ..._bf16out, 3 ..._view, 4 ..._view_bf16out (a window's size does not change
+ * the kernel: `wg` is that of a window over the whole output; the view forms take no statistics).  Returns the refusal code of
+ * that entry point for non-null arguments, AP_ERR_INVALID for a bad buffer or form.  One word group per launch, joined by "; ":
+ *   tsmall<1|2|4>                      conv_tsmall_f32<CO>
+ *   head<RB>                           conv_head_fwd_kernel<RB>, RB the rows per workgroup chosen at launch
+ *   small<S,Cout> staged|gather        conv_small_f32 (stride 1, LDS-staged) | conv_small_gather_f32 (stride 2)
+ *   direct<7,cop>                      conv_direct_f32<DirectCfg<7, cop>>
+ *   tapgemm th=<n>                     the tap GEMM body of the last 7x7 layer with its band height
+ *   igemm ConvCfg<CI,S,K,WCO,MT,WPX,NT> taps=<n>
+ *   bf3 Bf3Cfg<...>|Ph4Cfg<K> taps=<n> x3|b16 [ob16] [s2d3=ct|s2d3=mask] [phases=ph4|fused|4launch] wg=<workgroups>
+ *       x3 / b16: split / plain bf16 arithmetic; ob16: the bf16-storing instantiation; s2d3: the space-to-depth form of a 3x3
+ *       stride-2 layer with compile-time tap sets (ct) or run-time tap masks; phases: a transposed layer's four sub-pixel phases in
+ *       one tile, one launch, or four launches; wg: persistent workgroups (reads APAMD_BF3_BLOCKS as the launcher does).
+ * Kernel names are the registries' (ap_conv2d_kernel_name) without blanks.  ap_conv2d_fwd_route_names lists every kernel word
+ * the text can name, one per line ("tapgemm" without its th). */
+int ap_conv2d_fwd_route(const ap_conv_desc* d, int32_t with_stats, int32_t out_form, char* buf, int32_t buflen);
+int ap_conv2d_fwd_route_names(char* buf, int32_t buflen);
+
 /* ---- InstanceNorm2d(affine=False, eps) : networks.py:33-34 (F.instance_norm)
  * finalize: partial tiles -> mean[n,c], rstd[n,c] (biased variance); count = Hout*Wout.  y (nullable): the convolution
  * output the tiles were summed over ([NC][count]); when given, planes whose |mean| is many standard deviations -- where

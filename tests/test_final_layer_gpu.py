@@ -110,6 +110,11 @@ def test_final_layer_against_fp64(dev, name, precision):
         assert c['negative'] == 0.0
     y, names = run_layer(c, ops.PRECISION_BF16X3 if precision == 'bf16x3' else ops.PRECISION_FP32, dev)
     assert names == ['DirectCfg<7, 1>']             # one launch, the direct route, in either arithmetic
+    # ... and which body of that route ran: the tap GEMM in split-bf16 arithmetic, the vector-ALU kernel in fp32
+    spec = ops.ConvSpec([64], 1, 7, 1, 3, ops.PAD_REFLECT)
+    spec.precision = ops.PRECISION_BF16X3 if precision == 'bf16x3' else ops.PRECISION_FP32
+    route = ops.conv_fwd_route(spec, *c['x'].shape[0:1], *c['x'].shape[2:])
+    assert route.split()[0] == ('tapgemm' if precision == 'bf16x3' else 'direct<7,1>'), route
     assert y.shape == c['ref'].shape
     scale = float(c['pre'].abs().max())
     err = float((y.double().cpu() - c['ref']).abs().max()) / scale
