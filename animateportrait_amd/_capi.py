@@ -56,12 +56,13 @@ class ApWgradDesc(ctypes.Structure):
 
 
 # name -> (restype, argtypes); every symbol include/animateportrait_amd.h declares
-ABI_VERSION = 16     # AP_ABI_VERSION of include/animateportrait_amd.h this binding was written against
+ABI_VERSION = 17     # AP_ABI_VERSION of include/animateportrait_amd.h this binding was written against
 
 SIGNATURES = {
     'ap_abi_version': (ctypes.c_int32, []),
     'ap_version': (ctypes.c_char_p, []),
     'ap_last_error': (ctypes.c_char_p, []),
+    'ap_switch_names': (ctypes.c_int32, [ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
     'ap_conv2d_out_size': (ctypes.c_int, [ctypes.POINTER(ApConvDesc), ctypes.POINTER(ctypes.c_int32),
                                           ctypes.POINTER(ctypes.c_int32)]),
     'ap_conv2d_packed_floats': (ctypes.c_int64, [ctypes.POINTER(ApConvDesc)]),
@@ -218,6 +219,7 @@ SIGNATURES = {
 
 _lib = None
 _lock = threading.Lock()
+_switch_names = {}      # kind -> the APAMD_* variables of that kind the loaded library reads (ap_switch_names, asked once at load)
 
 
 def lib():
@@ -239,8 +241,19 @@ def lib():
                 if l.ap_abi_version() != ABI_VERSION:
                     raise RuntimeError('animateportrait_amd: %s speaks ABI %d, this binding ABI %d: rebuild the library '
                                        '(make -C animateportrait_amd/csrc)' % (LIB_PATH, l.ap_abi_version(), ABI_VERSION))
+                for kind in (0, 1, 2):
+                    buf = ctypes.create_string_buffer(l.ap_switch_names(kind, None, 0))
+                    l.ap_switch_names(kind, buf, len(buf))
+                    _switch_names[kind] = tuple(buf.value.decode().split())
                 _lib = l
     return _lib
+
+
+def switch_names(kind):
+    """The environment variables of one kind (0: route decisions, 1: tuning, 2: experiment builds) in the library's table
+    (csrc/switches.h)."""
+    lib()
+    return _switch_names[kind]
 
 
 def check(rc, what=''):

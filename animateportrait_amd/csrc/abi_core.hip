@@ -24,4 +24,17 @@ const char* ap_version(void) { return "animateportrait_amd 0.3 (gfx950)"; }
 int32_t ap_abi_version(void) { return AP_ABI_VERSION; }
 const char* ap_last_error(void) { return last_error_buf(); }
 
+int32_t ap_switch_names(int32_t kind, char* buf, int32_t cap) {
+    if (kind < SWK_ROUTE || kind > SWK_BUILD_ONLY || (!buf && cap > 0)) return fail(AP_ERR_INVALID, "switch_names: kind %d", kind);
+    int32_t need = 1;
+    for (int s = 0; s < SW_COUNT; ++s)
+        if (switch_row(s).kind == kind) need += (int32_t)strlen(switch_row(s).name) + 1;
+    if (need > cap) return need;
+    char* p = buf;
+    for (int s = 0; s < SW_COUNT; ++s)
+        if (switch_row(s).kind == kind) p += sprintf(p, "%s\n", switch_row(s).name);
+    *p = 0;
+    return need;
+}
+
 }  // extern "C"

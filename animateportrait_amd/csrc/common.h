@@ -8,6 +8,7 @@
 #include <mutex>
 #include <vector>
 #include "../../include/animateportrait_amd.h"
+#include "switches.h"      // sw(SW_...): the APAMD_* environment switches
 
 // Ablation switches (skip the DMA refill / the barriers / the epilogue of the matrix kernels, APAMD_ABLATE=<bits>)
 // exist only in the experiment build (`make ablate` -> libapamd_ablate.so, -DAPAMD_ABLATION); in the product library
@@ -32,11 +33,6 @@ template <class Seg>
 inline void fill_seg(Seg& seg, const ap_src& s, int chunk_begin, bool with_norm = true) {
     seg.data = s.data; seg.C = s.C; seg.chunk_begin = chunk_begin;
     if (with_norm) { seg.mean = s.mean; seg.rstd = s.rstd; seg.act = s.act; }
-}
-// A/B switches are integers on both sides of the boundary: APAMD_X=0 means "off", as ops.py reads it
-inline int env_int(const char* name, int dflt) {
-    const char* s = getenv(name);
-    return s ? atoi(s) : dflt;
 }
 // compute units of the current device (cached per device ordinal); without a device: the MI355X's 256
 inline int num_cus() {

@@ -233,7 +233,7 @@ static ConvKParams conv_params(const ap_conv_desc* d, const Plan& pl, const Laun
     p.tiles_x = L.tiles_x; p.tiles_y = L.tiles_y; p.co_tiles = pl.co_tiles;
     p.cin_pad = pl.cin_pad;
 #ifdef APAMD_ABLATION
-    p.ablate = env_int("APAMD_ABLATE", 0);
+    p.ablate = sw(SW_ABLATE);
 #endif
     return p;
 }
@@ -337,7 +337,7 @@ static void s2d3_params(ConvKParams& p, int div) {
 // persistent workgroups, each walks its share of the tiles: one per CU, two when two stage sets fit its 160 KB of LDS
 static unsigned bf3_workgroups(long long tiles, size_t lds, bool two_per_cu) {
     int cus = num_cus() * ((2 * lds <= 160 * 1024 || two_per_cu) ? 2 : 1);
-    if (const int forced = env_int("APAMD_BF3_BLOCKS", 0)) {      // tuning / test knob: never silent
+    if (const int forced = sw(SW_BF3_BLOCKS)) {      // tuning / test knob: never silent
         static bool told = false;
         if (!told) fprintf(stderr, "libapamd: APAMD_BF3_BLOCKS=%d overrides the persistent workgroup count\n", forced);
         told = true;
@@ -427,21 +427,21 @@ static int launch_bf3(const ap_conv_desc* d, const Plan& pl, const OutForm& o, c
         bool sb = false;
 #ifdef APAMD_VARIANTS
         if (!o.view && !o.octet && c.kern->K == 3 && c.kern->S == 1 && c.kern->TH == 16 && !c.kern->ROW && d->precision != AP_PRECISION_BF16 &&
-            p.osx == 1 && p.osy == 1 && p.oy_off == 0 && p.ox_off == 0 && env_int("APAMD_CONV_SB", 0)) {
+            p.osx == 1 && p.osy == 1 && p.oy_off == 0 && p.ox_off == 0 && sw(SW_CONV_SB)) {
             // rejected experiment kept for A/B (tools/variants/conv_bf16x3_sb.h, `make variants`): one LDS stage per
             // workgroup, two workgroups per CU
             kfn = bf3_sb_kernel(&lds);
             rc = ensure_dyn_lds(kfn, 160 * 1024);
             if (rc) return rc;
-            p.sb_skew = env_int("APAMD_CONV_SB_SKEW", 0);
+            p.sb_skew = sw(SW_CONV_SB_SKEW);
             sb = true;
         }
 #endif
 #ifdef APAMD_ABLATION
         // cycle account (tools/cycle_account.py): APAMD_STAMP_BUF = device address of the stamp buffer, APAMD_STAMP_WORDS =
         // dwords per wave; the stamps live in LDS behind the stage buffers, so only kernels that leave that room take them
-        if (const char* sb_ = getenv("APAMD_STAMP_BUF")) {
-            const int words = env_int("APAMD_STAMP_WORDS", 512);
+        if (const char* sb_ = sw_text(SW_STAMP_BUF)) {
+            const int words = sw(SW_STAMP_WORDS);
             if (!pl.ph4 && lds + (size_t)16 * words <= 160 * 1024) {
                 p.stamps = reinterpret_cast<unsigned*>(strtoull(sb_, nullptr, 0));
                 p.stamp_lds_off = (int)lds;

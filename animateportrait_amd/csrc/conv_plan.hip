@@ -141,7 +141,7 @@ static bool plan_direct(const ap_conv_desc* d, const Geom& g, Plan& pl) {
 // narrow 3x3 layers (landmark encoder): memory streams, one lane per output pixel (conv_small.h)
 static bool plan_small(const ap_conv_desc* d, const Geom& g, Plan& pl) {
     if (g.rowk || d->transposed || g.K != 3 || d->nsrc != 1 || pl.Cin > 16 || (d->Cout != 8 && d->Cout != 16) ||
-        d->w_layout != AP_W_OIHW || d->w_flip || env_int("APAMD_NO_SMALL", 0))
+        d->w_layout != AP_W_OIHW || d->w_flip || sw(SW_NO_SMALL))
         return false;
     pl.small = true;
     pl.nchunks = 1;
@@ -178,7 +178,7 @@ static int pick_bf3(const ap_conv_desc* d, const Geom& g, Plan& pl) {
         return pl.bk ? AP_OK : fail(AP_ERR_UNSUPPORTED, "no 1x%d row kernel", K);
     }
     if (d->precision == AP_PRECISION_FP32 || !(d->Cout >= 48 || (d->Cout >= 16 && pl.Cin >= 128)) || pl.Cin < 32 ||
-        env_int("APAMD_NO_BF16X3", 0))
+        sw(SW_NO_BF16X3))
         return AP_OK;
     for (int s = 0; s < d->nsrc; ++s)
         if (d->src[s].C % 16 != 0) return AP_OK;
@@ -206,7 +206,7 @@ static int pick_bf3(const ap_conv_desc* d, const Geom& g, Plan& pl) {
         const long long tiles = (long long)d->N * ((pl.Hout + tall->TH - 1) / tall->TH) * ((pl.Wout + 31) / 32) *
                                 ((d->Cout + tall->CO_TILE - 1) / tall->CO_TILE);
         // (also for maps no taller than the short tile: the column strip of a reflection-padded data gradient)
-        if ((tiles * 2 <= num_cus() || pl.Hout <= small->TH) && !env_int("APAMD_NO_SMALL_TILES", 0)) pl.bk = small;
+        if ((tiles * 2 <= num_cus() || pl.Hout <= small->TH) && !sw(SW_NO_SMALL_TILES)) pl.bk = small;
     }
     return AP_OK;
 }
@@ -214,7 +214,7 @@ static int pick_bf3(const ap_conv_desc* d, const Geom& g, Plan& pl) {
 // The fp32 implicit-GEMM kernel (conv_igemm.h), pl.k: cout tile by output width, channel chunk by the segments and the LDS budget
 static int pick_igemm(const ap_conv_desc* d, const Geom& g, Plan& pl) {
     int co_tile = d->Cout >= 96 ? 128 : (d->Cout >= 48 ? 64 : 32);
-    co_tile = env_int("APAMD_CONV_COTILE", co_tile);
+    if (const int forced = sw(SW_CONV_COTILE)) co_tile = forced;
     // channel chunk: largest of {8,4,2} that does not over-pad the narrowest segment, then shrink
     // until two workgroups fit a CU's LDS
     int minC = 1 << 30;
@@ -223,7 +223,7 @@ static int pick_igemm(const ap_conv_desc* d, const Geom& g, Plan& pl) {
     for (int s = 0; s < d->nsrc; ++s)
         while (ci > 2 && d->src[s].C % ci != 0 && d->src[s].C > ci) ci >>= 1;
     const int ntaps_max = d->transposed ? ((g.K + 1) / 2) * ((g.K + 1) / 2) : g.K * g.K;
-    const size_t lds_target = (size_t)env_int("APAMD_CONV_LDS_TARGET", 72 * 1024);
+    const size_t lds_target = (size_t)sw(SW_CONV_LDS_TARGET);
     for (;;) {
         const ConvKernelInfo* k = find_kernel(ci, g.S, g.KT, co_tile);
         if (!k) return fail(AP_ERR_UNSUPPORTED, "no kernel for CI=%d S=%d K=%d CO_TILE=%d", ci, g.S, g.KT, co_tile);
@@ -237,7 +237,7 @@ static int pick_igemm(const ap_conv_desc* d, const Geom& g, Plan& pl) {
         }
         ci >>= 1;
     }
-    if (const int forced = env_int("APAMD_CONV_CI", 0)) {
+    if (const int forced = sw(SW_CONV_CI)) {
         if (const ConvKernelInfo* k = find_kernel(forced, g.S, g.KT, co_tile)) { pl.k = k; ci = forced; }
     }
     layout_chunks(d, pl, ci);

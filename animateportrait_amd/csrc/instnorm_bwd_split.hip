@@ -304,10 +304,9 @@ using namespace apamd;
 extern "C" {
 
 int ap_instnorm_bwd_split_ok(int32_t C, int32_t H, int32_t W, int32_t g1_pad) {
-    const char* off = getenv("APAMD_NO_INBWD_SPLIT");      // (read per call: tests and A/B runs flip it inside one process)
     // H >= 4 for the fold: the kernel adds padded row 0 into row 1 and padded row H + 1 into row H - 2 in the lanes of those rows,
     // one border row per lane -- with H = 3 both land in row 1 and the second would be dropped
-    return !(off && atoi(off)) && C >= 8 && C % 8 == 0 && H >= 3 + g1_pad && W >= 8 && W % 8 == 0 && H <= 4096 && W <= 4096 &&
+    return !sw(SW_NO_INBWD_SPLIT) && C >= 8 && C % 8 == 0 && H >= 3 + g1_pad && W >= 8 && W % 8 == 0 && H <= 4096 && W <= 4096 &&
            H * W <= 4096 && (g1_pad == 0 || g1_pad == 1) ? 1 : 0;
 }
 

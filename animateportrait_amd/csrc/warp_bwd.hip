@@ -392,7 +392,7 @@ extern "C" int ap_warp_concat_bwd(const float* gout, const float* motion, const 
         return fail(AP_ERR_UNSUPPORTED, "warp_concat_bwd: H * W <= %d is served (got %d x %d)", INT_MAX / 2, H, W);
     hipError_t e = hipMemsetAsync(dx, 0, (size_t)N * C * H * W * sizeof(float), (hipStream_t)stream);
     if (e != hipSuccess) return fail(AP_ERR_LAUNCH, "warp_concat_bwd memset: %s", hipGetErrorString(e));
-    if (env_int("APAMD_WARP_BWD_PLAIN", 0)) {   // tap-by-tap scatter (kept for comparison); read per call
+    if (sw(SW_WARP_BWD_PLAIN)) {   // tap-by-tap scatter (kept for comparison); read per call
         hipLaunchKernelGGL(warp_concat_bwd_kernel, warp_grid((H * W + 255) / 256, C, N), dim3(256), 0, (hipStream_t)stream, gout,
                            motion, flow, ifmask, dx, C, H, W, S, flow_scale);
         return check_launch("warp_concat_bwd_kernel");

@@ -345,15 +345,14 @@ static const WarpFwdKernel kWarpFwdKernels[2][3] = {
 // A/B switch for tools/warp_fwd_bench.py: the quad-cooperative gather (channel-octet inputs, whole 256-pixel blocks of
 // 4-aligned rows, so that every quad is four live neighbours of one row)
 static bool quad_gather_route(int flags, int H, int W) {
-    const char* gather = getenv("APAMD_WARP_GATHER");           // read per call: tests flip it inside one process
-    const bool quad = gather && !strcmp(gather, "quad");
+    const bool quad = sw_is(SW_WARP_GATHER, "quad");            // read per call: tests flip it inside one process
     return quad && (flags & 2) && (W & 3) == 0 && W >= 4 && ((H * W) & 255) == 0;
 }
 
-// tile width (log2): 32 x 8 pixels when the map divides into them (APAMD_WARP_TILE = 0 / 4 / 5 / 6 for A/B runs, read once
-// per process), 0 = 256 consecutive pixels when it does not
+// tile width (log2): 32 x 8 pixels when the map divides into them (APAMD_WARP_TILE = 1 / 4 / 5 / 6 for A/B runs, read once
+// per process), 0 = 256 consecutive pixels when it does not or the variable asks for no tile
 static int warp_tile_shift(int H, int W) {
-    static const int tile_env = env_int("APAMD_WARP_TILE", 5);
+    static const int tile_env = sw(SW_WARP_TILE);
     if (tile_env < 4 || tile_env > 6 || (W & ((1 << tile_env) - 1)) || (H & ((256 >> tile_env) - 1))) return 0;
     return tile_env;
 }

@@ -158,7 +158,7 @@ static int launch_bf16_gemm(const ap_wgrad_desc* d, const WgradPlan& pl, const v
     p.m_tiles = pl.m_tiles; p.c_tiles = b.c_tiles;
     p.partial = partial;
 #ifdef APAMD_ABLATION
-    p.ablate = env_int("APAMD_ABLATE", 0);
+    p.ablate = sw(SW_ABLATE);
 #endif
     void* args[] = {&p};
     const unsigned nblk = (unsigned)(pl.m_tiles * b.c_tiles * pl.P);
@@ -192,7 +192,7 @@ static int launch_igemm(const ap_wgrad_desc* d, const WgradPlan& pl, float* work
     p.m_tiles = pl.m_tiles; p.q_tiles = g.q_tiles;
     p.partial = partial;
 #ifdef APAMD_ABLATION
-    p.ablate = env_int("APAMD_ABLATE", 0);
+    p.ablate = sw(SW_ABLATE);
 #endif
     void* args[] = {&p};
     const unsigned nblk = (unsigned)(pl.m_tiles * g.q_tiles * pl.P);

@@ -9,7 +9,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <climits>
 #include <string>
 
 namespace apamd {
@@ -86,8 +85,8 @@ static bool plan_narrow(const ap_wgrad_desc* d, WgradPlan& pl) {
 
 // APAMD_WGRAD_BLOCKS (tuning / test knob) in place of a family's own workgroup target; `tell`: never silent
 static int wgrad_block_target(int own, bool tell) {
-    const int forced = env_int("APAMD_WGRAD_BLOCKS", INT_MIN);
-    if (forced == INT_MIN) return own;
+    const int forced = sw(SW_WGRAD_BLOCKS);
+    if (!forced) return own;
     static std::atomic<bool> told{false};
     if (tell && !told.exchange(true)) fprintf(stderr, "libapamd: APAMD_WGRAD_BLOCKS=%d overrides the workgroup count\n", forced);
     return forced;
@@ -96,14 +95,14 @@ static int wgrad_block_target(int own, bool tell) {
 // which layer the bf16 GEMM kernel sees (Kb / Cb / Hb / Wb), or false: the layer is not on the bf16 matrix pipe
 static bool bf16_gemm_view(const ap_wgrad_desc* d, const WgradPlan& pl, Bf16GemmPlan& b) {
     const int S = d->stride, K = d->K;
-    const bool no_bf = env_int("APAMD_NO_BF16X3", 0) != 0;
+    const bool no_bf = sw(SW_NO_BF16X3) != 0;
     const bool bf_ok = d->precision != AP_PRECISION_FP32 && d->M >= 48 && !no_bf;
     b.Kb = K; b.Cb = pl.Cin; b.Hb = d->H; b.Wb = d->W;
     // stride-2 3x3 / 4x4 pad-1 layers (the generator's encoder, the PatchGAN body): the space-to-depth form -- a 2 x 2
     // stride-1 layer over 4 Cin channels -- runs on the same bf16 GEMM kernel (16x the fp32 MFMA rate per product; a
     // 3x3 layer carries 7 of 16 all-zero taps along)
     b.s2d = bf_ok && S == 2 && (K == 3 || K == 4) && d->pad == 1 && d->pad_mode == AP_PAD_ZERO && pl.Cin >= 8 &&
-            d->H % 2 == 0 && d->W % 2 == 0 && !env_int("APAMD_NO_S2D_WGRAD", 0);
+            d->H % 2 == 0 && d->W % 2 == 0 && !sw(SW_NO_S2D_WGRAD);
     if (b.s2d) { b.Kb = 2; b.Cb = 4 * pl.Cin; b.Hb = d->H / 2 + 1; b.Wb = d->W / 2 + 1; }
     // 7x7 stems on a few channels (the generator's three input layers): the row form -- a 1 x 7 layer over 7 Cin channels -- as the
     // forward pass runs them (ap_split_prepass_rows); one 64-channel tile holds up to 9 input channels
@@ -112,7 +111,7 @@ static bool bf16_gemm_view(const ap_wgrad_desc* d, const WgradPlan& pl, Bf16Gemm
     // 256 x 256 into pixel-octet slots (~140 us) and the row view padded from 21 to the kernel's 64 channels (~210 us, 277 MB
     // written) -- so the whole operator is ~470 us and 1.1 GB more HBM traffic per stem against 433 us on the fp32 kernel (and ~680 us
     // with three products and both parts).  Kept for the tests and as the starting point of a 32-channel tile.
-    b.rows = d->precision == AP_PRECISION_BF16 && d->M >= 24 && !no_bf && env_int("APAMD_ROWS_WGRAD", 0) && S == 1 && K == 7 &&
+    b.rows = d->precision == AP_PRECISION_BF16 && d->M >= 24 && !no_bf && sw(SW_ROWS_WGRAD) && S == 1 && K == 7 &&
              d->pad == 3 && d->nsrc == 1 && pl.Cin * 7 <= 64;
     if (b.rows) b.Cb = 7 * pl.Cin;
     if (!(b.s2d || b.rows || (bf_ok && S == 1 && (K == 3 || K == 4) && pl.Cin >= 32))) return false;
@@ -202,7 +201,7 @@ static bool xs_copies_serve(const ap_wgrad_desc* d, const WgradPlan& pl) {
 
 // ... re-tiled into the kernel's layout (xs_transpose_kernel) in place of normalising + splitting the fp32 tensors again
 bool wgrad_xs_route(const ap_wgrad_desc* d, const WgradPlan& pl) {
-    return xs_copies_serve(d, pl) && !env_int("APAMD_NO_XS_WGRAD", 0);
+    return xs_copies_serve(d, pl) && !sw(SW_NO_XS_WGRAD);
 }
 
 // (the kernels index a copy's 16-byte slots with 32 bits)
@@ -210,7 +209,7 @@ static bool xs_slots_fit(int N, int C, int H, int W) { return (long long)N * 2 *
 
 // ... both operands straight from the split copies (wgrad_xs.h): no operand preparation at all
 bool wgrad_xs_direct_ok(const ap_wgrad_desc* d, const WgradPlan& pl) {
-    if (!xs_copies_serve(d, pl) || env_int("APAMD_NO_XS_DIRECT", 0) || d->M % 8 != 0) return false;
+    if (!xs_copies_serve(d, pl) || sw(SW_NO_XS_DIRECT) || d->M % 8 != 0) return false;
     const bool split = d->precision == AP_PRECISION_BF16X3;
     if (!xs_slots_fit(d->N, d->M, d->GH, d->GW)) return false;
     // the 2 x 2 layer over the space-to-depth view (split-bf16 only)

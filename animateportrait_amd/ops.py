@@ -9,6 +9,7 @@ activation that the CONSUMER applies while it stages the tensor into LDS.  This 
 import collections
 import ctypes
 import os
+import re
 
 import torch
 
@@ -41,9 +42,44 @@ PRECISION_FP32, PRECISION_BF16X3, PRECISION_BF16 = 0, 1, 2
 PRECISION_BY_NAME = {'fp32': PRECISION_FP32, 'bf16x3': PRECISION_BF16X3, 'bf16': PRECISION_BF16}
 DEFAULT_PRECISION = PRECISION_BY_NAME.get(os.environ.get('APAMD_PRECISION', 'bf16x3'), PRECISION_BF16X3)
 
+_ATOI = re.compile(rb'\s*[+-]?\d+')
+
+
+def _switch(name, default=0, word=False):
+    """The APAMD_* switch ``name`` by the one parse rule of both sides of the C ABI (csrc/switches.h): unset, empty, not a number
+    or 0 means ``default``, any other integer means that value.  word: a value that is no number comes back as it is (the cache key
+    of a word-valued switch, APAMD_WARP_GATHER=quad).
+    (the dict behind os.environ: backward_switches() asks ~20 times per layer and pass, and for an unset variable os.environ.get
+    is an encode, a KeyError and its handler)"""
+    raw = os.environ._data.get(name.encode())
+    if not raw:
+        return default
+    m = _ATOI.match(raw)
+    return (int(m.group()) or default) if m else (raw if word else default)
+
+
+# The switches that Python itself reads, with the module global each one sets at import (tests, tools and bench.py assign the
+# globals afterwards).  The core library's own switches are the table of csrc/switches.h; plan_switch_names() lists them.
+# APAMD_NO_XS_WGRAD and APAMD_NO_XS_DIRECT stand in both tables, as two halves of one decision: the Python global decides what the
+# weight-gradient descriptor CARRIES (the forward pass's split copies), the C switch, read per call, what the planner ACCEPTS
+# (wgrad_plan.hip: wgrad_xs_route, wgrad_xs_direct_ok).  Set in the environment before the import, the variable turns both off.
+_STREAM_FENCE = not _switch('APAMD_NO_STREAM_FENCE')        # the fence of _stream()
+BF16_RAW = not _switch('APAMD_NO_BF16_RAW')                 # plain-bf16 training stores the trunk's raw outputs as bf16 (below)
+# the weight gradients' shifted operand re-tiled from the forward pass's split copies (ap_wgrad_desc.src_xs); 1 turns it off
+XS_WGRAD = not _switch('APAMD_NO_XS_WGRAD')
+# ... and, where the gradient's split copy exists too, both operands read as split copies by the kernel itself (ap_conv2d_wgrad_xs)
+XS_DIRECT = XS_WGRAD and not _switch('APAMD_NO_XS_DIRECT')
+# the inference trunk's raw outputs in the channel-octet layout (round 6; tests flip it to compare with the NCHW route)
+OCTET_TRUNK = not _switch('APAMD_NO_OCTET_TRUNK')
+# plain-bf16 arithmetic: the 7x7 edge layers' weight gradients on the bf16 matrix pipe (wgrad_k7.h); 1: the fp32 / vector-ALU kernels (A/B)
+K7_WGRAD = not _switch('APAMD_NO_K7_WGRAD')
+# ... and the PatchGAN's first layer as an output stream on the matrix pipe (conv_d0.h); 1: the fp32 implicit-GEMM kernel (A/B)
+D0_MFMA = K7_WGRAD and not _switch('APAMD_NO_D0_MFMA')
+# read per call, in s2d_eligible
+_PER_CALL_SWITCHES = ('APAMD_NO_S2D', 'APAMD_NO_S2D3')
+
 
 _LAST_STREAM = {}          # device index -> torch stream of this package's previous launch
-_STREAM_FENCE = os.environ.get('APAMD_NO_STREAM_FENCE', '0') != '1'
 
 
 def _stream():
@@ -89,11 +125,6 @@ def _require_device(t, name, allow_bf16=False):
 # -1.1 GB of memory, and only -0.4 ms of 56 -- the passes that read these tensors (norm_split, instnorm_bwd_split, the padded-row
 # operand transposition) run at 3.5-4.4 TB/s because of latency / issue, not bandwidth: with 8-byte instead of 16-byte loads per
 # lane they take as long per launch.
-BF16_RAW = os.environ.get('APAMD_NO_BF16_RAW', '0') != '1'
-# the weight gradients' shifted operand re-tiled from the forward pass's split copies (ap_wgrad_desc.src_xs); 1 turns it off
-XS_WGRAD = os.environ.get('APAMD_NO_XS_WGRAD', '0') != '1'
-# ... and, where the gradient's split copy exists too, both operands read as split copies by the kernel itself (ap_conv2d_wgrad_xs)
-XS_DIRECT = XS_WGRAD and os.environ.get('APAMD_NO_XS_DIRECT', '0') != '1'
 
 
 class Feat:
@@ -470,11 +501,11 @@ def s2d_eligible(spec, h, w):
     # (3x3: split arithmetic only -- measured +1 % on the generator forward; in plain bf16 the stride-2 kernel already
     # shares a CU with a second workgroup and the space-to-depth copy costs more than it saves: 60.3 -> 62.0 ms train step)
     k_ok = spec.k == 4 or (spec.k == 3 and spec.precision == PRECISION_BF16X3 and spec.cin_segments[0] % 16 == 0 and
-                           not os.environ.get('APAMD_NO_S2D3'))
+                           not _switch('APAMD_NO_S2D3'))
     return (spec.precision != PRECISION_FP32 and k_ok and spec.stride == 2 and spec.pad == 1 and
             spec.pad_mode == PAD_ZERO and not spec.transposed and len(spec.cin_segments) == 1 and
             spec.cin_segments[0] >= 32 and spec.cin_segments[0] % 8 == 0 and spec.cout >= 48 and h % 2 == 0 and
-            w % 2 == 0 and spec.w_layout == W_OIHW and not spec.w_flip and not os.environ.get('APAMD_NO_S2D'))
+            w % 2 == 0 and spec.w_layout == W_OIHW and not spec.w_flip and not _switch('APAMD_NO_S2D'))
 
 
 def s2d_spec(spec):
@@ -577,10 +608,6 @@ def trunk_octet_ok(c, residual=None, keep_fp32=False):
     return residual is None or (residual.is_split_only and residual.xs is not None and not residual.xs_heads_only and residual.oct is None)
 
 
-# the inference trunk's raw outputs in the channel-octet layout (round 6; tests flip it to compare with the NCHW route)
-OCTET_TRUNK = os.environ.get('APAMD_NO_OCTET_TRUNK', '0') != '1'
-
-
 def wants_split(c):
     """Whether a materialised residual-trunk feature of ``c`` channels is going to be staged by a split-bf16
     convolution: its consumers are c -> c 3x3 layers, so this is the C library's eligibility rule (>= 48 outputs,
@@ -664,10 +691,6 @@ def conv2d(spec, srcs, packed, bias=None, act=ACT_NONE, want_stats=False, out_ac
 # Inference: the ResNet trunk's residual stream is kept only as split copies (materialize keep_fp32=False; HISTORY.md section 3.10).
 # (tests flip the flag to compare with the fp32 stream)
 RESIDUAL_AS_SPLIT = True
-# plain-bf16 arithmetic: the 7x7 edge layers' weight gradients on the bf16 matrix pipe (wgrad_k7.h); 0: the fp32 / vector-ALU kernels (A/B)
-K7_WGRAD = os.environ.get('APAMD_NO_K7_WGRAD', '0') != '1'
-# ... and the PatchGAN's first layer as an output stream on the matrix pipe (conv_d0.h); 0: the fp32 implicit-GEMM kernel (A/B)
-D0_MFMA = K7_WGRAD and os.environ.get('APAMD_NO_D0_MFMA', '0') != '1'
 
 
 OUT_PLAIN, OUT_OCTET, OUT_BF16, OUT_VIEW, OUT_VIEW_BF16 = range(5)      # out_form of ap_conv2d_fwd_route
@@ -858,16 +881,23 @@ def _wgrad_buffers(nfloats, what, out, out_shape, device):
     return ws, _grad_out(out, out_shape, device)
 
 
-# Everything the backward route decisions read besides the forms of the tensors (form_of): the module switches and the environment
-# variables the C side reads per call for its plan queries (wgrad_plan.hip: make_wgrad_plan, the xs predicates; conv_plan.hip:
-# make_plan behind ap_conv2d_wants_presplit; ap_instnorm_bwd_split_ok) and s2d_eligible reads here.  Tests and A/B runs flip them
-# inside one process: every cached decision is keyed by backward_switches().  A new switch of a backward route is listed HERE.
-_WGRAD_XS_ENV = ('APAMD_NO_XS_DIRECT', 'APAMD_NO_XS_WGRAD', 'APAMD_NO_BF16X3', 'APAMD_NO_S2D_WGRAD', 'APAMD_ROWS_WGRAD',
-                 'APAMD_NO_INBWD_SPLIT', 'APAMD_NO_S2D', 'APAMD_NO_SMALL', 'APAMD_NO_SMALL_TILES')
+_PLAN_SWITCHES = None
+
+
+def plan_switch_names():
+    """Every environment variable a route decision reads per call: the route and tuning rows of the core library's table
+    (csrc/switches.h; ap_switch_names, asked once when the library is loaded) and the two that s2d_eligible reads here."""
+    global _PLAN_SWITCHES
+    if _PLAN_SWITCHES is None:
+        _PLAN_SWITCHES = C.switch_names(0) + C.switch_names(1) + _PER_CALL_SWITCHES
+    return _PLAN_SWITCHES
 
 
 def backward_switches():
-    return (DEFAULT_PRECISION, XS_WGRAD, XS_DIRECT, K7_WGRAD, D0_MFMA, BF16_RAW) + tuple(os.environ.get(v) for v in _WGRAD_XS_ENV)
+    """Everything the backward route decisions read besides the forms of the tensors (form_of): the module switches and the parsed
+    values of plan_switch_names().  Tests and A/B runs flip them inside one process: every cached decision is keyed by this."""
+    return (DEFAULT_PRECISION, XS_WGRAD, XS_DIRECT, K7_WGRAD, D0_MFMA, BF16_RAW) + tuple(
+        [_switch(v, 0, True) for v in _PLAN_SWITCHES or plan_switch_names()])
 
 
 # (k, stride, pad, pad_mode) of the edge layers that have kernels of their own

@@ -101,10 +101,15 @@ typedef struct ap_conv_desc {
  * ap_instnorm_finalize and gave ap_conv_desc.reserved a meaning as s2d_k without one).  A binding compares
  * ap_abi_version() with the AP_ABI_VERSION it was written against at load time and refuses a mismatch
  * (animateportrait_amd/_capi.py does). */
-#define AP_ABI_VERSION 16
+#define AP_ABI_VERSION 17
 int32_t ap_abi_version(void);
 const char* ap_version(void);
 const char* ap_last_error(void);
+/* The APAMD_* environment variables of one kind that the library reads at run time (csrc/switches.h holds the table and the
+ * parse rule), newline-separated and NUL-terminated in buf.  kind 0: route decisions, 1: tuning of a chosen route, 2: rows
+ * of the experiment builds only.  Returns the bytes needed, NUL included; buf is written only when cap holds them.  A binding
+ * keys whatever it caches of the library's route decisions with the values of kinds 0 and 1. */
+int32_t ap_switch_names(int32_t kind, char* buf, int32_t cap);
 
 /* ---- convolution: nn.Conv2d / nn.ConvTranspose2d (+ fused pad, bias, act, IN statistics)
  * replaces F.conv2d / F.conv_transpose2d / F.pad(reflect) launched by

@@ -22,7 +22,8 @@ UNREACHABLE = T.IGEMM_UNREACHABLE | {'Bf3Cfg<1,7,1,2,4,4,0,1>'}
 
 @pytest.fixture
 def plan_env(monkeypatch):
-    for v in T.PLAN_ENV:
+    from animateportrait_amd import ops
+    for v in ops.plan_switch_names():
         monkeypatch.delenv(v, raising=False)
     return monkeypatch
 

@@ -46,8 +46,6 @@ NONE, RELU, LRELU = 0, 1, 2
 OIHW, IOHW = 0, 1
 PLAIN, OCTET, OB16 = 0, 1, 2
 TAIL_FLOATS = 4096
-PLAN_ENV = ('APAMD_NO_SMALL', 'APAMD_NO_BF16X3', 'APAMD_NO_SMALL_TILES', 'APAMD_CONV_COTILE', 'APAMD_CONV_LDS_TARGET',
-            'APAMD_CONV_CI', 'APAMD_BF3_BLOCKS')
 
 # vsrc: activation of a virtual first source act(IN(raw)), or None: plain;  stats: a statistics buffer is passed;  form: PLAIN | OCTET |
 # OB16;  refused: the entry point's (and the query's) refusal code for this form instead of a route
@@ -451,8 +449,8 @@ def _bits(t):
 @pytest.mark.gpu
 @pytest.mark.parametrize('case', CASES, ids=[k.name for k in CASES])
 def test_conv_edge(dev, monkeypatch, case):
-    from animateportrait_amd import _capi
-    for v in PLAN_ENV:
+    from animateportrait_amd import _capi, ops
+    for v in ops.plan_switch_names():
         monkeypatch.delenv(v, raising=False)
     # 1 route
     assert query(case) == (case.refused if case.refused else case.route)

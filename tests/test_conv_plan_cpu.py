@@ -18,9 +18,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'con
 FP32, BF16X3, BF16 = 0, 1, 2
 ZERO, REFLECT = 0, 1
 OIHW, IOHW = 0, 1
-# every environment switch make_plan and the *_ok predicates read
-PLAN_ENV = ('APAMD_NO_SMALL', 'APAMD_NO_BF16X3', 'APAMD_NO_SMALL_TILES', 'APAMD_CONV_COTILE', 'APAMD_CONV_LDS_TARGET',
-            'APAMD_CONV_CI')
 CONFIGS = {'default': {}, 'no_small_tiles': {'APAMD_NO_SMALL_TILES': '1'}, 'no_bf16x3': {'APAMD_NO_BF16X3': '1'}}
 CONFIG_ORDER = ('default', 'no_small_tiles', 'no_bf16x3')
 COUTS = (1, 2, 4, 8, 16, 32, 48, 64, 96, 128, 256, 512)
@@ -141,7 +138,8 @@ def _table(lib):
 
 
 def _use(env, setenv, delenv):
-    for v in PLAN_ENV:
+    from animateportrait_amd import ops
+    for v in ops.plan_switch_names():      # every environment switch a route decision reads: make_plan's and the *_ok predicates' among them
         delenv(v)
     for k, v in env.items():
         setenv(k, v)

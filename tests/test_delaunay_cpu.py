@@ -20,8 +20,8 @@ def test_served_region_corners(n, p, tcap, served):
 
 def test_abi_version_and_export_count():
     from animateportrait_amd import _capi as C
-    assert C.ABI_VERSION == 16 and C.lib().ap_abi_version() == 16
-    assert len(C.SIGNATURES) == 95 and 'ap_delaunay' in C.SIGNATURES and 'ap_delaunay_ok' in C.SIGNATURES
+    assert C.ABI_VERSION == 17 and C.lib().ap_abi_version() == 17
+    assert len(C.SIGNATURES) == 96 and 'ap_delaunay' in C.SIGNATURES and 'ap_delaunay_ok' in C.SIGNATURES
 
 
 def test_refused_calls_return_an_error_without_a_device():

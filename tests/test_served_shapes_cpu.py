@@ -183,7 +183,7 @@ def test_wgrad_xs_route_cache_follows_every_input(monkeypatch, lib):
     # descriptors only: the plan reads shapes and which pointers are set, never the memory behind them
     monkeypatch.setattr(ops, '_require_device', lambda *a, **k: None)
     monkeypatch.setattr(ops, '_WGRAD_XS_OK', {})
-    for v in ops._WGRAD_XS_ENV:
+    for v in ops.plan_switch_names():
         monkeypatch.delenv(v, raising=False)
     monkeypatch.setattr(ops, 'DEFAULT_PRECISION', ops.PRECISION_BF16X3)
     monkeypatch.setattr(ops, 'XS_WGRAD', True)

@@ -21,7 +21,8 @@ SPLIT_T_FORMS = {'general', 'vec', 'pad_rows', 's2d_rows'}
 
 @pytest.fixture
 def plan_env(monkeypatch):
-    for v in T.PLAN_ENV:
+    from animateportrait_amd import ops
+    for v in ops.plan_switch_names():
         monkeypatch.delenv(v, raising=False)
     return monkeypatch
 

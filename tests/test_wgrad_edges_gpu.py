@@ -39,7 +39,6 @@ FP32, X3, B16 = 0, 1, 2
 ZERO, REFLECT = 0, 1
 NONE, RELU, LRELU = 0, 1, 2
 TAIL_FLOATS = 4096
-PLAN_ENV = ('APAMD_NO_BF16X3', 'APAMD_NO_S2D_WGRAD', 'APAMD_ROWS_WGRAD', 'APAMD_NO_XS_DIRECT', 'APAMD_NO_XS_WGRAD', 'APAMD_WGRAD_BLOCKS')
 
 # via: 'wgrad' ap_conv2d_wgrad | 'pre' ap_conv2d_wgrad_pre (g_t from instnorm_bwd_split) | 'xs' ap_conv2d_wgrad_xs (g as a split copy)
 #      | 'final' | 'few' (routes of ops.wgrad);  xs: which forward copies the source carries: '' | 'plain' | 's2d'
@@ -396,7 +395,7 @@ def blocks_with_a_ragged_split(case, setenv):
 @pytest.mark.parametrize('case', CASES, ids=[k.name for k in CASES])
 def test_wgrad_edge(dev, monkeypatch, case):
     from animateportrait_amd import ops
-    for v in PLAN_ENV:
+    for v in ops.plan_switch_names():
         monkeypatch.delenv(v, raising=False)
     for k, v in case.env.items():
         monkeypatch.setenv(k, v)

@@ -24,9 +24,6 @@ import pytest
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'wgrad_plans.json')
 FP32, BF16X3, BF16 = 0, 1, 2
 ZERO, REFLECT = 0, 1
-# every environment switch make_wgrad_plan and the xs predicates read
-PLAN_ENV = ('APAMD_NO_BF16X3', 'APAMD_NO_S2D_WGRAD', 'APAMD_ROWS_WGRAD', 'APAMD_NO_XS_DIRECT', 'APAMD_NO_XS_WGRAD',
-            'APAMD_WGRAD_BLOCKS')
 CONFIGS = {'default': {}, 'no_bf16x3': {'APAMD_NO_BF16X3': '1'}, 'no_s2d': {'APAMD_NO_S2D_WGRAD': '1'},
            'rows': {'APAMD_ROWS_WGRAD': '1'}, 'no_xs_direct': {'APAMD_NO_XS_DIRECT': '1'}, 'no_xs': {'APAMD_NO_XS_WGRAD': '1'},
            'blocks64': {'APAMD_WGRAD_BLOCKS': '64'}}
@@ -197,7 +194,8 @@ def _listed(p, lay, shp):
 
 
 def _use(env, setenv, delenv):
-    for v in PLAN_ENV:
+    from animateportrait_amd import ops
+    for v in ops.plan_switch_names():      # every environment switch a route decision reads: make_wgrad_plan's and the xs predicates' among them
         delenv(v)
     for k, v in env.items():
         setenv(k, v)
